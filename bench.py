@@ -1,14 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- etcd WAL replay-and-verify on MI355X (BASELINE.json metric).
 
-Default line (value, ms_per_step, roofline, cpu_baseline): configs[1] -- one
+Default line (value, ms_per_step, roofline): configs[1] -- one
 step = one (*WAL).ReadAll (wal/wal.go:164-216) over a GPU-resident synthetic
 WAL of 8 GiB of mixed 64 B - 64 KiB entries (log-uniform sizes, xorshift
 payload) with one corrupt record at frame k = 0.73 N, so every step must
 report walpb.ErrCRCMismatch at frame k.  The whole WAL is read and verified
-each step (the GPU pipeline does not stop early).  The same line carries
-`configs`: every other BASELINE config timed in the same run, each with its
-own ms_per_step, roofline and (N=1) cpu_baseline --
+each step (the GPU pipeline does not stop early).  A plain run does only
+that: set up, warm up, time --steps ReadAlls, print the line.
+
+--dump-outputs DIR writes what the last timed step returned (result.npy,
+records.npy: see dump_outputs) so that two builds can be compared output for
+output; the inputs are seeded, identical from run to run.
+
+--full adds everything else to the same line: the cpu_baseline legs, the
+headline's extras (cold first-call and reserve times, the clean WAL timed in
+the loop, the PCIe-inclusive rate) and `configs`: every other BASELINE config
+timed in the same run, each with its own ms_per_step, roofline and (N=1)
+cpu_baseline --
   c1      configs[0]: the 1M x 256 B WAL (wal.Save) replayed on the GPU
   shards  configs[2]: 512 per-raft-group WALs x 64 MiB per GPU (4096 over
           8 GPUs), one batched ReadAll per step, one RCCL all-reduce
@@ -47,9 +56,17 @@ def parse():
     ap.add_argument("--size-gib", type=float, default=8.0)
     ap.add_argument("--min-data", type=int, default=64)
     ap.add_argument("--max-data", type=int, default=65536)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baselines, the headline's "
+                         "first-call / clean-WAL / PCIe-inclusive extras and the other BASELINE configs (--configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned as DIR/result.npy and "
+                         "DIR/records.npy (float64; workloads wal and c1)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines (a run without --full never times them)")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="with --full: skip the headline's PCIe-inclusive pass")
     ap.add_argument("--snap-files", type=int, default=10000)
     ap.add_argument("--pool-gib", type=float, default=None,
                     help="snapstream's pinned host pool per rank (default 24 GiB at N=1, max(6, 48 / N) at N>1: "
@@ -67,14 +84,20 @@ def parse():
     ap.add_argument("--shards-per-gpu", type=int, default=512)
     ap.add_argument("--shard-mib", type=int, default=64)
     ap.add_argument("--configs", default="c1,shards,snap,snapstream,commit,rewind,split2",
-                    help="default line: the other BASELINE configs timed in the same run ('none' to skip)")
+                    help="with --full: the other BASELINE configs timed in the same run ('none' to skip)")
     ap.add_argument("--sub-cpu-seconds", type=float, default=6.0,
                     help="CPU-baseline time per leg of each `configs` sub-result")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for N>1 (nccl = RCCL; gloo only to rehearse the N>1 path)")
     ap.add_argument("--one-device", action="store_true",
                     help="rehearsal on a 1-GPU box: every rank on cuda:0 (with --dist-backend gloo)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.dump_outputs and a.workload not in ("wal", "c1"):
+        ap.error("--dump-outputs is implemented for --workload wal and c1")
+    if not a.full:   # a plain run times its own steps only
+        a.no_cpu_baseline = a.no_e2e = True
+        a.configs = "none"
+    return a
 
 
 def load_traffic(kernel="k_stream", workload=None):
@@ -962,6 +985,37 @@ def run_msg(a, dist, rank, world, local):
     return out
 
 
+RESULT_FIELDS = ("status", "detail", "fail_record", "fail_offset", "n_records", "enti", "last_crc", "n_ents",
+                 "has_state", "state_term", "state_vote", "state_commit", "metadata_off", "metadata_len")
+RECORD_FIELDS = ("offset", "data_off", "data_len", "type", "crc", "chained_crc")
+DUMP_MAX_ROWS = (48 << 20) // (8 * len(RECORD_FIELDS))   # records.npy stays under 48 MiB
+
+
+def dump_outputs(dirpath, ctx, rs, n):
+    """What the caller of the last timed ReadAll holds, as float64 arrays:
+    result.npy   the ewal_result fields RESULT_FIELDS, in that order (those
+                 after `enti` are defined for an OK status only: 0 otherwise,
+                 as wal._collect reports them)
+    records.npy  one row of RECORD_FIELDS per frame of that ReadAll's chain
+                 (ewal_copy_records); above DUMP_MAX_ROWS frames a fixed,
+                 seeded sample of the rows in frame order
+    (every value is an integer below 2^53 here, so float64 holds it exactly)."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    ok = rs.status == L.OK
+    res = [float(getattr(rs, f)) if ok or i < 6 else 0.0 for i, f in enumerate(RESULT_FIELDS)]
+    np.save(os.path.join(dirpath, "result.npy"), np.array(res, dtype=np.float64))
+    arr = (L.RecordDesc * max(n, 1))()
+    got = L.lib.ewal_copy_records(ctx.handle, arr, n)
+    assert got == n, (got, n)
+    raw = np.frombuffer(arr, dtype=np.dtype([("offset", "<u8"), ("data_off", "<u8"), ("data_len", "<u8"),
+                                             ("type", "<i8"), ("crc", "<u4"), ("chained_crc", "<u4")]), count=n)
+    if n > DUMP_MAX_ROWS:
+        raw = raw[np.sort(np.random.default_rng(0).choice(n, size=DUMP_MAX_ROWS, replace=False))]
+    recs = np.stack([raw[f].astype(np.float64) for f in RECORD_FIELDS], axis=1)
+    np.save(os.path.join(dirpath, "records.npy"), recs)
+
+
 def run_wal(a, dist, rank, world, local, size, min_data, max_data, label, cpu_seconds, full=True):
     """configs[1] (and configs[0]'s WAL as `c1`): one ReadAll per step over a
     GPU-resident WAL per rank with one corrupt record at frame 0.73 N.  full:
@@ -1009,8 +1063,11 @@ def run_wal(a, dist, rank, world, local, size, min_data, max_data, label, cpu_se
         extra["clean_ms_per_step"] = round(timed(dist, a.steps, clean_step) / a.steps * 1e3, 4)
         extra["clean_pipeline_device_ms"] = round(rs.device_ms, 4)
     k = int(0.73 * n)
-    rec = W.records(ctx, n)[k]
-    p = rec["data_off"] + rec["data_len"] // 2
+    recs = (L.RecordDesc * n)()
+    got = L.lib.ewal_copy_records(ctx.handle, recs, n)
+    assert got == n, (got, n)
+    p = recs[k].data_off + recs[k].data_len // 2
+    del recs
     flip = bytearray(dbuf.download(1, p))
     flip[0] ^= 0x5A
     dbuf.upload(bytes(flip), p)
@@ -1043,6 +1100,8 @@ def run_wal(a, dist, rank, world, local, size, min_data, max_data, label, cpu_se
     post_avg = sum(post_ms) / len(post_ms)
     fr_avg = sum(fr_ms) / len(fr_ms)
     achieved = nb / (stream_avg / 1e3) / 1e9
+    if a.dump_outputs and rank == 0:   # before any other call on ctx: the last timed step's own result
+        dump_outputs(a.dump_outputs, ctx, rs, n)
 
     # ---- end-to-end variant (host -> device included), one pass -------------
     if full and not a.no_e2e:
@@ -1273,7 +1332,8 @@ def main():
         else:
             label = "configs[1]" if (a.size_gib, a.min_data, a.max_data) == (8.0, 64, 65536) else "configs[1]-shaped"
             out = run_wal(a, dist, rank, world, local, int(a.size_gib * (1 << 30)), a.min_data, a.max_data, label,
-                          a.cpu_seconds)
+                          a.cpu_seconds, full=a.full)
+            a.dump_outputs = None   # (the headline's; the c1 sub-line below runs through run_wal too)
             subs = [x for x in a.configs.split(",") if x and x != "none"] if a.workload == "wal" else []
             if subs:
                 out["configs"] = {}

@@ -28,7 +28,7 @@ def fake_workloads(monkeypatch):
 
 
 def _main(monkeypatch, capsys, configs):
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--configs", configs])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--configs", configs])   # (the sub-lines are --full's)
     rc = bench.main()
     out = capsys.readouterr().out.strip().splitlines()
     return rc, json.loads(out[-1])
@@ -54,3 +54,21 @@ def test_failed_sub_line_exits_nonzero(fake_workloads, monkeypatch, capsys):
     assert "AssertionError" in line["configs"]["split2"]["error"]
     # the other sub-lines and the headline are still reported
     assert line["ms_per_step"] == 1.5 and line["configs"]["commit"]["ms_per_step"] == 1.5
+
+
+def test_plain_run_times_the_headline_alone(monkeypatch, capsys):
+    """Without --full: one run_wal call (full=False, no CPU baseline, no PCIe
+    pass), no sub-line -- whatever --configs says."""
+    calls = []
+
+    def fake_wal(a, *args, **k):
+        calls.append((a.no_cpu_baseline, a.no_e2e, k.get("full")))
+        return _line("wal")
+
+    monkeypatch.setattr(bench, "run_wal", fake_wal)
+    monkeypatch.setattr(bench, "SUBS", {name: None for name in bench.SUBS})   # (calling one would raise)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.main() == 0
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert calls == [(True, True, False)]
+    assert "configs" not in line and "failed_configs" not in line and line["ms_per_step"] == 1.5

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread \
   > "$out/pytest_gpu.txt" 2>&1
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$out/smoke.txt" 2>&1
-timeout -k 10 600 python3 bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"
+timeout -k 10 600 python3 bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"
 p="$out/prof"
 mkdir -p "$p"
 for w in wal c1 shards snap commit rewind; do
