@@ -546,7 +546,8 @@ int ewal_save_device(ewal_ctx *ctx, const void *d_data, uint64_t data_len_total,
                      uint64_t *h_rec_off);
 
 /* ---- CRC primitives (pkg/crc, pkg/crc/crc.go:23-41) ---------------------- */
-/* crc32.Update(crc, MakeTable(poly), p) on a DEVICE buffer. */
+/* crc32.Update(crc, MakeTable(poly), p) on a DEVICE buffer.  d_buf must be
+ * 16-byte aligned (EWAL_E_INVAL otherwise, when n > 0). */
 int ewal_crc32_update_device(ewal_ctx *ctx, uint32_t crc, uint32_t poly, const void *d_buf, uint64_t n,
                              uint32_t *out);
 /* crc32.Update on host memory (SSE4.2 for Castagnoli) -- for small writes. */
@@ -558,7 +559,8 @@ uint32_t ewal_crc32_combine(uint32_t poly, uint32_t crc_a, uint32_t crc_b, uint6
 /* ---- snapshots: snap.loadSnap / Snapshotter.Load, snap/snapshotter.go:62-111 */
 /* Batch-verify snapshot FILES (snappb.Snapshot envelopes) resident in one
  * device buffer at offs[i], lens[i].  status[i] = EWAL_OK / EWAL_ERR_SNAP_CRC /
- * unmarshal class; crc outputs are the stored and recomputed CRCs. */
+ * unmarshal class; crc outputs are the stored and recomputed CRCs.  d_buf
+ * must be 16-byte aligned (EWAL_E_INVAL otherwise); offs[i] may be any byte. */
 int esnap_verify_packed(ewal_ctx *ctx, const void *d_buf, uint64_t buf_len, const uint64_t *offs,
                         const uint64_t *lens, uint32_t n, uint32_t poly, int32_t *status,
                         uint32_t *stored_crc, uint32_t *computed_crc);
