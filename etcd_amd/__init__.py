@@ -4,7 +4,7 @@ Product layout:
   csrc/        HIP kernels (gfx950) + host C++ behind the C ABI in include/ewal.h
   libewal.so   built in-tree by build.sh
   wal.py       mirror of the reference `wal` package (OpenAtIndex/ReadAll/Create/...)
-  snap.py      mirror of `snap.Snapshotter` (Load / snapNames / batch verify)
+  snap.py      mirror of `snap.Snapshotter` (Load / snapNames / batch verify; SaveSnap / batched save)
   raftcommit.py batched `raft.maybeCommit` (SoA arrays or 192-B group records)
   crc.py       `pkg/crc` digest (chained CRC-32C) over host or device buffers
   raftmsg.py   batched `raftpb.Message` decode (the /raft ingress)
@@ -14,5 +14,7 @@ Product layout:
 """
 from . import _lib  # noqa: F401  (fails loudly if libewal.so is missing)
 from .wal import Context, OpenAtIndex, Create, Encoder, readall_bytes, synth_wal  # noqa: F401
+from .snap import save_packed, save_dir, snap_name  # noqa: F401
 
-__all__ = ["Context", "OpenAtIndex", "Create", "Encoder", "readall_bytes", "synth_wal"]
+__all__ = ["Context", "OpenAtIndex", "Create", "Encoder", "readall_bytes", "synth_wal", "save_packed", "save_dir",
+           "snap_name"]

@@ -148,6 +148,16 @@ class SnapshotDesc(C.Structure):
                 ("removed", C.c_uint64 * 64)]
 
 
+class SnapSaveRec(C.Structure):   # esnap_save_rec
+    _fields_ = [("index", C.c_uint64), ("term", C.c_uint64), ("data_off", C.c_uint64), ("data_len", C.c_uint64),
+                ("nodes_off", C.c_uint64), ("n_nodes", C.c_uint64), ("removed_off", C.c_uint64),
+                ("n_removed", C.c_uint64), ("unrec_off", C.c_uint64), ("unrec_len", C.c_uint64)]
+
+
+class SnapSaved(C.Structure):     # esnap_saved
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint64), ("crc", C.c_uint32), ("pad", C.c_uint32)]
+
+
 vp = C.c_void_p
 u8p = C.POINTER(C.c_uint8)
 _SIGS = {
@@ -248,6 +258,16 @@ _SIGS = {
                                       C.POINTER(C.c_uint32)]),
     "esnap_copy_snapshot": (C.c_int, [vp, C.c_uint32, C.POINTER(SnapshotDesc)]),
     "esnap_load_dir": (C.c_int, [vp, C.c_char_p, C.c_uint32, C.POINTER(SnapshotDesc), C.POINTER(C.c_char_p)]),
+    "esnap_save_bound": (C.c_uint64, [C.POINTER(SnapSaveRec), C.c_uint32, C.POINTER(C.c_uint64)]),
+    "esnap_save_packed_device": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(SnapSaveRec), C.c_uint32,
+                                           C.POINTER(C.c_uint64), C.c_char_p, C.c_uint32, vp, C.c_uint64,
+                                           C.POINTER(SnapSaved)]),
+    "esnap_snap_name": (None, [C.c_uint64, C.c_uint64, C.c_char_p]),
+    "esnap_save_dir": (C.c_int, [vp, C.c_char_p, vp, C.c_uint64, C.POINTER(SnapSaveRec), C.POINTER(C.c_uint64),
+                                 C.c_char_p, C.c_uint32, C.POINTER(vp)]),
+    "esnap_save_tile_bytes": (C.c_uint32, []),
+    "esnap_save_rec_size": (C.c_uint32, []),
+    "esnap_saved_size": (C.c_uint32, []),
     "ecommit_batch_device": (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]),
     "ecommit_batch_rec_device": (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]),
 }

@@ -10,14 +10,18 @@
 // on this path; without a GPU every call returns EWAL_E_NODEVICE.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
+#include <fcntl.h>
+#include <unistd.h>
 #include <algorithm>
 #include <cstdio>
+#include <cerrno>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <set>
+#include <string>
 #include <vector>
 
 #include "crc_math.h"
@@ -26,7 +30,9 @@
 #include "msg_kernels.hip"
 #include "frame_fields.hip"
 #include "frame_kernels.hip"
+#include "snap_save.hip"
 #include "ewal_stage.h"
+#include "ewal_wire.h"
 
 #define EW_CHECK(x)                                                          \
   do {                                                                       \
@@ -151,6 +157,12 @@ struct ewal_ctx {
   std::vector<int32_t> snap_rmap;
   std::vector<uint64_t> snap_rfirst, snap_rcnt;
   DevBuf sgather, ssegs, srlist, sgoff, srcnt, srfirst;
+  // esnap_save_packed_device: tiles, per-file table, head / trailer bytes,
+  // tile remainders, results (device), and the host arrays they are built in
+  DevBuf svtiles, svfiles, svmeta, svrem, svout;
+  std::vector<SaveTile> sv_htiles;
+  std::vector<SaveFile> sv_hfiles;
+  std::vector<uint8_t> sv_hmeta;
   std::vector<ewal_unrec> unrec;   // XXX_unrecognized of the last ReadAll's result (side list)
   uint64_t unrec_bytes = 0;
   // the side arena of split byte fields (Record.Data / Entry.Data repeated
@@ -2939,6 +2951,153 @@ int esnap_verify_packed(ewal_ctx *c, const void *d_buf, uint64_t buf_len, const 
     if (stored_crc) stored_crc[i] = h[i].stored;
     if (computed_crc) computed_crc[i] = h[i].computed;
   }
+  return EWAL_OK;
+}
+
+uint32_t esnap_save_tile_bytes(void) { return ESS_TILE; }
+
+static_assert(ESS_TILE == (1u << ESS_TILE_LOG) && ESS_TILE % 8192 == 0, "a tile is whole pairs of 4 KiB units");
+int esnap_save_packed_device(ewal_ctx *c, const void *d_data, uint64_t data_len_total, const esnap_save_rec *recs,
+                             uint32_t n, const uint64_t *h_u64, const uint8_t *h_unrec, uint32_t poly, void *d_out,
+                             uint64_t cap, esnap_saved *out) {
+  if (!c || (n && (!recs || !out || !d_out)) || (!d_data && data_len_total)) return EWAL_E_INVAL;
+  if ((((uintptr_t)d_data | (uintptr_t)d_out) & 15) != 0) return EWAL_E_INVAL;
+  if (n == 0) return EWAL_OK;
+  const uintptr_t pd = (uintptr_t)d_data, po = (uintptr_t)d_out;
+  if (pd + data_len_total < pd || po + cap < po) return EWAL_E_INVAL;
+  if (data_len_total && cap && pd < po + cap && po < pd + data_len_total) return EWAL_E_INVAL;
+  for (uint32_t i = 0; i < n; ++i) {
+    const esnap_save_rec &r = recs[i];
+    uint64_t e;
+    if (__builtin_add_overflow(r.data_off, r.data_len, &e) || e > data_len_total) return EWAL_E_INVAL;
+    if ((r.n_nodes || r.n_removed) && !h_u64) return EWAL_E_INVAL;
+    if (r.unrec_len && !h_unrec) return EWAL_E_INVAL;
+    if (r.n_nodes > (1ull << 56) || r.n_removed > (1ull << 56) || r.unrec_len > (1ull << 62) ||
+        __builtin_add_overflow(r.nodes_off, r.n_nodes, &e) || e > (1ull << 60) ||
+        __builtin_add_overflow(r.removed_off, r.n_removed, &e) || e > (1ull << 60) ||
+        __builtin_add_overflow(r.unrec_off, r.unrec_len, &e))
+      return EWAL_E_INVAL;
+  }
+  // the layout: file i's body starts hmax (its longest envelope header) past
+  // the previous file's end, plus the 0..15 bytes that make Data's
+  // destination congruent to its source mod 16; the header is written
+  // right-aligned against the body once the CRC is known
+  std::vector<SaveTile> &tiles = c->sv_htiles;
+  std::vector<SaveFile> &files = c->sv_hfiles;
+  std::vector<uint8_t> &meta = c->sv_hmeta;
+  tiles.clear();
+  files.resize(n);
+  meta.clear();
+  uint64_t pos = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const esnap_save_rec &r = recs[i];
+    SaveFile &f = files[i];
+    const uint64_t *nodes = r.n_nodes ? h_u64 + r.nodes_off : nullptr;
+    const uint64_t *rem = r.n_removed ? h_u64 + r.removed_off : nullptr;
+    f.src = r.data_off;
+    f.dlen = r.data_len;
+    f.hlen = (uint32_t)ewal_wire::snap_head_size(r.data_len);
+    f.tlen = ewal_wire::snap_trailer_size(nodes, r.n_nodes, r.index, r.term, rem, r.n_removed, r.unrec_len);
+    if (__builtin_add_overflow(f.hlen + f.tlen, r.data_len, &f.blen)) return EWAL_E_INVAL;
+    f.meta = meta.size();
+    meta.resize(meta.size() + f.hlen + f.tlen);
+    uint8_t *m = meta.data() + f.meta;
+    *m = 0x0a;
+    ewal_wire::put_varint(m + 1, r.data_len);
+    ewal_wire::snap_trailer_marshal(m + f.hlen, nodes, r.n_nodes, r.index, r.term, rem, r.n_removed,
+                                    r.unrec_len ? h_unrec + r.unrec_off : nullptr, r.unrec_len);
+    uint64_t b0;
+    if (__builtin_add_overflow(pos, (uint64_t)ewal_wire::snap_env_max(f.blen), &b0)) return EWAL_E_NOMEM;
+    f.body = b0 + ((r.data_off - (b0 + f.hlen)) & 15);
+    if (__builtin_add_overflow(f.body, f.blen, &pos) || pos > cap) return EWAL_E_NOMEM;
+    // tiles over Data's 16-B aligned middle
+    const uint64_t a = std::min<uint64_t>(r.data_len, (16 - (r.data_off & 15)) & 15);
+    const uint64_t mid = (r.data_len - a) & ~15ull;
+    f.tile0 = tiles.size();
+    const uint64_t nt = (mid + ESS_TILE - 1) / ESS_TILE;
+    if (nt > 0xffffffffull) return EWAL_E_INVAL;
+    f.ntiles = (uint32_t)nt;
+    for (uint32_t k = 0; k < f.ntiles; ++k) tiles.push_back(SaveTile{i, k});
+  }
+  if (tiles.size() > 0xffffffffull) return EWAL_E_INVAL;
+  EW_CHECK(hipSetDevice(c->device));
+  DevTables *tb;
+  int rc = get_tables(c, poly, &tb);
+  if (rc) return rc;
+  const ewal::CrcTables &ht = *c->host_tables[poly];
+  for (uint32_t i = 0; i < n; ++i) {
+    SaveFile &f = files[i];
+    f.chead = ht.raw(0xffffffffu, meta.data() + f.meta, f.hlen);
+    f.ltrail = ht.raw(0, meta.data() + f.meta + f.hlen, (size_t)f.tlen);
+  }
+  const uint32_t nt = (uint32_t)tiles.size();
+  EW_CHECK(c->svfiles.ensure((size_t)n * sizeof(SaveFile)));
+  EW_CHECK(c->svmeta.ensure(meta.size()));
+  EW_CHECK(c->svout.ensure((size_t)n * sizeof(esnap_saved)));
+  EW_CHECK(c->svtiles.ensure((size_t)std::max<uint32_t>(nt, 1) * sizeof(SaveTile)));
+  EW_CHECK(c->svrem.ensure((size_t)std::max<uint32_t>(nt, 1) * 4));
+  EW_CHECK(hipMemcpyAsync(c->svfiles.p, files.data(), (size_t)n * sizeof(SaveFile), hipMemcpyHostToDevice, c->stream));
+  EW_CHECK(hipMemcpyAsync(c->svmeta.p, meta.data(), meta.size(), hipMemcpyHostToDevice, c->stream));
+  if (nt)
+    EW_CHECK(hipMemcpyAsync(c->svtiles.p, tiles.data(), (size_t)nt * sizeof(SaveTile), hipMemcpyHostToDevice, c->stream));
+  EW_CHECK(hipEventRecord(c->ev0, c->stream));
+  if (nt) {
+    const unsigned grid = (unsigned)std::min<uint64_t>(grid_for(nt, ESS_WAVES), (uint64_t)std::max(1, c->num_cu));
+    hipLaunchKernelGGL(k_snap_copy, dim3(grid), dim3(ESS_THREADS), 0, c->stream, (const uint8_t *)d_data,
+                       (uint8_t *)d_out, (const SaveTile *)c->svtiles.as<SaveTile>(), nt,
+                       (const SaveFile *)c->svfiles.as<SaveFile>(), tb->slice, tb->shift,
+                       c->svrem.as<uint32_t>());
+  }
+  hipLaunchKernelGGL(k_snap_finish, dim3(n), dim3(ESS_FIN_THREADS), 0, c->stream, (const uint8_t *)d_data,
+                     (uint8_t *)d_out, (const SaveFile *)c->svfiles.as<SaveFile>(),
+                     (const uint8_t *)c->svmeta.as<uint8_t>(), (const uint32_t *)c->svrem.as<uint32_t>(), tb->slice,
+                     tb->shift, c->svout.as<esnap_saved>());
+  EW_CHECK(hipGetLastError());
+  EW_CHECK(hipEventRecord(c->ev1, c->stream));
+  EW_CHECK(hipMemcpyAsync(out, c->svout.p, (size_t)n * sizeof(esnap_saved), hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  return EWAL_OK;
+}
+
+// Snapshotter.SaveSnap (snap/snapshotter.go:39-44): the file built on the GPU,
+// downloaded and written as ioutil.WriteFile does.
+int esnap_save_dir(ewal_ctx *ctx, const char *dirpath, const void *d_data, uint64_t data_len_total,
+                   const esnap_save_rec *rec, const uint64_t *h_u64, const uint8_t *h_unrec, uint32_t poly,
+                   char **out_name) {
+  if (out_name) *out_name = nullptr;
+  if (!ctx || !dirpath || !rec) return EWAL_E_INVAL;
+  if (rec->index == 0) return EWAL_OK;   // raft.IsEmptySnap
+  const uint64_t cap = esnap_save_bound(rec, 1, h_u64);
+  if (cap == ~0ull) return EWAL_E_INVAL;
+  void *d_out = nullptr;
+  int rc = ewal_device_alloc(ctx, cap, &d_out);
+  if (rc) return rc;
+  esnap_saved sv{};
+  rc = esnap_save_packed_device(ctx, d_data, data_len_total, rec, 1, h_u64, h_unrec, poly, d_out, cap, &sv);
+  std::vector<uint8_t> b;
+  if (rc == EWAL_OK) {
+    b.resize(sv.len);
+    rc = ewal_download(ctx, b.data(), (const uint8_t *)d_out + sv.off, sv.len);
+  }
+  ewal_device_free(ctx, d_out);
+  if (rc) return rc;
+  char name[39];
+  esnap_snap_name(rec->term, rec->index, name);
+  const std::string path = std::string(dirpath) + "/" + name;
+  const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);   // ioutil.WriteFile
+  if (fd < 0) return EWAL_E_IO;
+  size_t done = 0;
+  while (done < b.size()) {
+    const ssize_t w = ::write(fd, b.data() + done, b.size() - done);
+    if (w < 0) {
+      if (errno == EINTR) continue;
+      ::close(fd);
+      return EWAL_E_IO;
+    }
+    done += (size_t)w;
+  }
+  if (::close(fd) != 0) return EWAL_E_IO;
+  if (out_name) *out_name = strdup(name);
   return EWAL_OK;
 }
 

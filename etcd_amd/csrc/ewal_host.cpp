@@ -637,4 +637,34 @@ int esnap_load_dir(ewal_ctx *ctx, const char *dirpath, uint32_t poly, esnap_snap
   return err;
 }
 
+// ---- Snapshotter.SaveSnap / save, snap/snapshotter.go:39-60 -----------------
+uint32_t esnap_save_rec_size(void) { return (uint32_t)sizeof(esnap_save_rec); }
+uint32_t esnap_saved_size(void) { return (uint32_t)sizeof(esnap_saved); }
+
+// Per file: the longest envelope header, up to 15 bytes that bring Data's
+// destination to its source's residue mod 16, the body.
+uint64_t esnap_save_bound(const esnap_save_rec *recs, uint32_t n, const uint64_t *h_u64) {
+  uint64_t tot = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const esnap_save_rec &r = recs[i];
+    const uint64_t *nodes = r.n_nodes ? h_u64 + r.nodes_off : nullptr;
+    const uint64_t *rem = r.n_removed ? h_u64 + r.removed_off : nullptr;
+    uint64_t blen = ewal_wire::snap_head_size(r.data_len);
+    if (__builtin_add_overflow(blen, r.data_len, &blen)) return ~0ull;
+    // every node is at most 11 bytes: the counts cannot wrap the trailer's size
+    if (r.n_nodes > (1ull << 56) || r.n_removed > (1ull << 56) || r.unrec_len > (1ull << 62)) return ~0ull;
+    if (__builtin_add_overflow(blen, (uint64_t)ewal_wire::snap_trailer_size(nodes, r.n_nodes, r.index, r.term, rem,
+                                                                            r.n_removed, r.unrec_len), &blen))
+      return ~0ull;
+    if (__builtin_add_overflow(tot, blen, &tot) ||
+        __builtin_add_overflow(tot, (uint64_t)ewal_wire::snap_env_max(blen) + 15, &tot))
+      return ~0ull;
+  }
+  return tot;
+}
+
+void esnap_snap_name(uint64_t term, uint64_t index, char *out) {
+  std::snprintf(out, 39, "%016llx-%016llx.snap", (unsigned long long)term, (unsigned long long)index);
+}
+
 }  // extern "C"

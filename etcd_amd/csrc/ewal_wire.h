@@ -56,4 +56,30 @@ inline uint8_t *frame_write(uint8_t *o, int64_t type, uint32_t crc, const uint8_
   return o;
 }
 
+// raftpb.Snapshot.MarshalTo, raft/raftpb/raft.pb.go:954-999, around Data: the
+// head `0a v(len(Data))` (always written: nil and empty Data encode alike) and
+// the trailer {10 v(node)}* 18 v(Index) 20 v(Term) {28 v(removed)}*
+// XXX_unrecognized.
+inline size_t snap_head_size(uint64_t dlen) { return 1 + sov(dlen); }
+inline size_t snap_trailer_size(const uint64_t *nodes, uint64_t n_nodes, uint64_t index, uint64_t term,
+                                const uint64_t *removed, uint64_t n_removed, uint64_t unrec_len) {
+  size_t r = 1 + sov(index) + 1 + sov(term) + unrec_len;
+  for (uint64_t k = 0; k < n_nodes; ++k) r += 1 + sov(nodes[k]);
+  for (uint64_t k = 0; k < n_removed; ++k) r += 1 + sov(removed[k]);
+  return r;
+}
+inline uint8_t *snap_trailer_marshal(uint8_t *o, const uint64_t *nodes, uint64_t n_nodes, uint64_t index,
+                                     uint64_t term, const uint64_t *removed, uint64_t n_removed,
+                                     const uint8_t *unrec, uint64_t unrec_len) {
+  for (uint64_t k = 0; k < n_nodes; ++k) { *o++ = 0x10; o = put_varint(o, nodes[k]); }
+  *o++ = 0x18; o = put_varint(o, index);
+  *o++ = 0x20; o = put_varint(o, term);
+  for (uint64_t k = 0; k < n_removed; ++k) { *o++ = 0x28; o = put_varint(o, removed[k]); }
+  if (unrec_len) std::memcpy(o, unrec, unrec_len);
+  return o + unrec_len;
+}
+// snappb.Snapshot{Crc, Data}.MarshalTo, snap/snappb/snap.pb.go:158-176: the
+// envelope header `08 v(crc) 12 v(len(body))`; its longest form (a 5-byte crc)
+inline size_t snap_env_max(uint64_t blen) { return 1 + 5 + 1 + sov(blen); }
+
 }  // namespace ewal_wire

@@ -9,6 +9,10 @@
   (esnap_verify_packed; snap/snapshotter.go:76-111).
 * `load_dir` -- Snapshotter.Load (newest first, tried failures renamed
   .broken; snap/snapshotter.go:62-74); `snap_names` -- snapNames.
+* `save_packed` -- Snapshotter.save's bytes for a batch of snapshots whose
+  Data is on the device, in one fused copy + CRC pass
+  (esnap_save_packed_device; snap/snapshotter.go:46-60); `save_dir` --
+  SaveSnap for one snapshot (snap/snapshotter.go:39-44); `snap_name`.
 * `snapshot` / `copy_field` -- the full decoded raftpb.Snapshot (Data over
   repeated fields, Nodes / RemovedNodes past 64, XXX_unrecognized).
 """
@@ -104,3 +108,69 @@ def snap_names(dirpath):
     buf = C.create_string_buffer(max(1, need.value))
     lib.esnap_names(dirpath.encode(), buf, need.value, C.byref(need))
     return buf.raw[:need.value].decode().split("\0")[:n]
+
+
+# bytes of Data per tile of the fused save pass (0: an older A/B build, EWAL_LIB_PATH, without the save entry points)
+SAVE_TILE = lib.esnap_save_tile_bytes() if hasattr(lib, "esnap_save_tile_bytes") else 0
+
+
+def snap_name(term, index):
+    """The file name Snapshotter.save uses, "%016x-%016x.snap" % (term, index)."""
+    buf = C.create_string_buffer(39)
+    lib.esnap_snap_name(term, index, buf)
+    return buf.value.decode()
+
+
+def _save_args(snaps):
+    """snaps: dicts with data_off, data_len and optionally index, term, nodes,
+    removed, unrec -> (esnap_save_rec[], h_u64, h_unrec)."""
+    n = len(snaps)
+    recs = (L.SnapSaveRec * max(n, 1))()
+    u64, unrec = [], bytearray()
+    for r, s in zip(recs, snaps):
+        nodes, removed, un = list(s.get("nodes", ())), list(s.get("removed", ())), bytes(s.get("unrec") or b"")
+        r.index, r.term = s.get("index", 0), s.get("term", 0)
+        r.data_off, r.data_len = s["data_off"], s["data_len"]
+        r.nodes_off, r.n_nodes = len(u64), len(nodes)
+        u64 += nodes
+        r.removed_off, r.n_removed = len(u64), len(removed)
+        u64 += removed
+        r.unrec_off, r.unrec_len = len(unrec), len(un)
+        unrec += un
+    return recs, (C.c_uint64 * max(len(u64), 1))(*u64), bytes(unrec)
+
+
+def save_bound(snaps):
+    """esnap_save_bound: a capacity of the output buffer that is always enough."""
+    recs, u64, _ = _save_args(snaps)
+    return lib.esnap_save_bound(recs, len(snaps), u64)
+
+
+def save_packed(ctx, dbuf, data_len, snaps, dout, cap, poly=L.CASTAGNOLI):
+    """Snapshotter.save's bytes for every snapshot of snaps (dicts: data_off,
+    data_len into dbuf[0, data_len); index, term, nodes, removed, unrec) into
+    the device buffer dout[0, cap): [(off, len, crc)] -- file i is
+    dout[off, off + len), the library chooses the offsets."""
+    n = len(snaps)
+    recs, u64, unrec = _save_args(snaps)
+    out = (L.SnapSaved * max(n, 1))()
+    check(lib.esnap_save_packed_device(ctx.handle, dbuf.ptr, data_len, recs, n, u64, unrec, poly, dout.ptr, cap, out))
+    return [(o.off, o.len, o.crc) for o in out[:n]]
+
+
+def save_dir(ctx, dirpath, dbuf, data_len, snap, poly=L.CASTAGNOLI):
+    """Snapshotter.SaveSnap: writes dirpath/<snap_name(term, index)> and
+    returns the name; None (nothing written) for an empty snapshot (index 0)."""
+    recs, u64, unrec = _save_args([snap])
+    name = C.c_void_p()
+    check(lib.esnap_save_dir(ctx.handle, dirpath.encode(), dbuf.ptr, data_len, recs, u64, unrec, poly, C.byref(name)))
+    if not name.value:
+        return None
+    out = C.string_at(name.value).decode()
+    _libc.free(name)
+    return out
+
+
+_libc = C.CDLL(None)
+_libc.free.argtypes = [C.c_void_p]
+_libc.free.restype = None

@@ -596,6 +596,69 @@ int esnap_load_dir(ewal_ctx *ctx, const char *dirpath, uint32_t poly, esnap_snap
  * Returns the count (0: ErrNoSnapshot) or a negative error. */
 int64_t esnap_names(const char *dirpath, char *out, uint64_t cap, uint64_t *len);
 
+/* ---- snapshots: Snapshotter.save / SaveSnap, snap/snapshotter.go:39-60 ---- */
+/* One raftpb.Snapshot to save (a HOST array, one per snapshot).  Data is the
+ * device range d_data[data_off, data_off + data_len) at any byte offset;
+ * Nodes / RemovedNodes are ranges of the host array h_u64 (in uint64 units),
+ * XXX_unrecognized a range of the host bytes h_unrec (unrec_len 0: nil). */
+typedef struct esnap_save_rec {
+  uint64_t index, term;
+  uint64_t data_off, data_len;
+  uint64_t nodes_off, n_nodes;
+  uint64_t removed_off, n_removed;
+  uint64_t unrec_off, unrec_len;
+} esnap_save_rec;
+/* Where file i landed in d_out, and the CRC stored in it. */
+typedef struct esnap_saved {
+  uint64_t off, len;
+  uint32_t crc, pad;
+} esnap_saved;
+/* A capacity of d_out that esnap_save_packed_device never exceeds for these
+ * records (the files' bytes plus at most 19 bytes of layout slack per file);
+ * from the host arrays alone.  ~0 when the sum does not fit 64 bits. */
+uint64_t esnap_save_bound(const esnap_save_rec *recs, uint32_t n, const uint64_t *h_u64);
+/* Snapshotter.save's bytes (snap/snapshotter.go:46-60) for n snapshots in ONE
+ * call on the ctx's stream:
+ *   b    = raftpb.Snapshot.Marshal()       raft/raftpb/raft.pb.go:954-999
+ *   crc  = crc32.Update(0, MakeTable(poly), b)
+ *   file = snappb.Snapshot{Crc, Data: b}.Marshal()   snap/snappb/snap.pb.go:158-176
+ * File i is d_out[out[i].off, out[i].off + out[i].len), byte-identical to the
+ * reference's; out[i].crc is its stored CRC.  The offsets are OUTPUTS: the
+ * library places every file so that its Data lands at an address congruent
+ * to its source mod 16 (the copy is then aligned 16-byte loads and stores).
+ * Files are in order of i, do not overlap, lie inside [0, cap), may have
+ * small gaps between them, and no byte of d_out outside the files is written
+ * -- the output feeds esnap_verify_packed directly.  One fused pass: every
+ * byte of Data is loaded from HBM once and stored once, its CRC contribution
+ * taken from the registers of that load (etcd_amd/csrc/snap_save.hip).
+ * d_data and d_out are DEVICE buffers, 16-byte aligned, that do not overlap.
+ * Decided on the host before any kernel is launched (d_out untouched):
+ *   EWAL_E_INVAL  a Data range outside d_data, a range that wraps, d_out
+ *                 overlapping d_data, a base pointer not 16-byte aligned
+ *   EWAL_E_NOMEM  the layout needs more than cap (cap >= esnap_save_bound()
+ *                 is always enough)
+ * n == 0: EWAL_OK, nothing written. */
+int esnap_save_packed_device(ewal_ctx *ctx, const void *d_data, uint64_t data_len_total, const esnap_save_rec *recs,
+                             uint32_t n, const uint64_t *h_u64, const uint8_t *h_unrec, uint32_t poly, void *d_out,
+                             uint64_t cap, esnap_saved *out);
+/* The file name save uses, "%016x-%016x.snap" % (term, index)
+ * (snap/snapshotter.go:47): 38 characters; out: 39 bytes with the NUL. */
+void esnap_snap_name(uint64_t term, uint64_t index, char *out);
+/* Snapshotter.SaveSnap (snap/snapshotter.go:39-44) for one snapshot: nothing
+ * is written when raft.IsEmptySnap holds (index == 0, raft/node.go:79-81):
+ * EWAL_OK with *out_name = NULL.  Otherwise the file is built on the GPU,
+ * downloaded, and written to dirpath/<esnap_snap_name> with mode 0666,
+ * truncating an existing file (ioutil.WriteFile); *out_name (malloc'd, the
+ * caller frees it with free()) is its name.  I/O failures: EWAL_E_IO. */
+int esnap_save_dir(ewal_ctx *ctx, const char *dirpath, const void *d_data, uint64_t data_len_total,
+                   const esnap_save_rec *rec, const uint64_t *h_u64, const uint8_t *h_unrec, uint32_t poly,
+                   char **out_name);
+/* For bindings: bytes of Data per tile of the fused pass, sizeof(esnap_save_rec),
+ * sizeof(esnap_saved). */
+uint32_t esnap_save_tile_bytes(void);
+uint32_t esnap_save_rec_size(void);
+uint32_t esnap_saved_size(void);
+
 /* ---- raft quorum commit: raft.maybeCommit, raft/raft.go:248-258 ---------- */
 /* Batched over G independent raft groups (SoA).  match[v*G + g] for voter
  * v < nvoters[g] (1..255); log terms for group g are log_terms[log_ptr[g] ..
