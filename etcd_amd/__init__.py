@@ -7,7 +7,7 @@ Product layout:
   snap.py      mirror of `snap.Snapshotter` (Load / snapNames / batch verify; SaveSnap / batched save)
   raftcommit.py batched `raft.maybeCommit` (SoA arrays or 192-B group records)
   crc.py       `pkg/crc` digest (chained CRC-32C) over host or device buffers
-  raftmsg.py   batched `raftpb.Message` decode (the /raft ingress)
+  raftmsg.py   batched `raftpb.Message` decode (the /raft ingress) and Marshal (the egress)
   shard.py     per-rank shard assignment, the RCCL summary all-reduce and the
                torch.distributed exchange of ONE WAL's split ranges (C join)
   _lib.py      ctypes bindings of include/ewal.h

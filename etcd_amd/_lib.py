@@ -78,6 +78,19 @@ class SegmentDesc(C.Structure):   # emsg_segment
     _fields_ = [("kind", C.c_int32), ("pad", C.c_int32), ("ent", C.c_int64), ("off", C.c_uint64), ("len", C.c_uint64)]
 
 
+class OutMsg(C.Structure):   # emsg_out
+    _fields_ = [("type", C.c_uint64), ("to", C.c_uint64), ("from_", C.c_uint64), ("term", C.c_uint64),
+                ("log_term", C.c_uint64), ("index", C.c_uint64), ("commit", C.c_uint64), ("ents_first", C.c_uint64),
+                ("n_ents", C.c_uint64), ("snap_index", C.c_uint64), ("snap_term", C.c_uint64),
+                ("snap_data_off", C.c_uint64), ("snap_data_len", C.c_uint64), ("snap_nodes_off", C.c_uint64),
+                ("snap_n_nodes", C.c_uint64), ("snap_removed_off", C.c_uint64), ("snap_n_removed", C.c_uint64),
+                ("reject", C.c_int32), ("pad", C.c_int32)]
+
+
+class Encoded(C.Structure):   # emsg_encoded
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint64)]
+
+
 SNAP_FIELD_DATA, SNAP_FIELD_UNREC, SNAP_FIELD_NODES, SNAP_FIELD_REMOVED = range(4)
 SEG_UNREC, SEG_ENTRY_UNREC, SEG_ENTRY_DATA, SEG_SNAP_UNREC, SEG_SNAP_DATA, SEG_SNAP_NODE, SEG_SNAP_REMOVED = range(7)
 
@@ -185,6 +198,13 @@ _SIGS = {
                                            C.c_uint32, C.POINTER(MessageDesc), C.POINTER(C.c_uint64)]),
     "emsg_copy_entries": (C.c_int64, [vp, C.c_uint64, C.POINTER(EntryDesc), C.c_int64]),
     "emsg_copy_segments": (C.c_int64, [vp, C.c_uint64, C.POINTER(SegmentDesc), C.c_int64]),
+    "emsg_encode_batch_device": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp,
+                                           C.c_uint64, C.POINTER(Encoded), C.POINTER(C.c_uint64)]),
+    "emsg_encode_size": (C.c_uint64, [C.POINTER(OutMsg), C.c_uint64, C.POINTER(EntryDesc), C.c_uint64,
+                                      C.POINTER(C.c_uint64), C.c_uint64]),
+    "emsg_encode_tile_bytes": (C.c_uint32, []),
+    "emsg_out_size": (C.c_uint32, []),
+    "emsg_encoded_size": (C.c_uint32, []),
     "esnap_copy_field": (C.c_int64, [vp, C.c_uint32, C.c_int32, vp, C.c_int64]),
     "ewal_batch_copy_entries": (C.c_int64, [vp, C.c_uint64, C.POINTER(EntryDesc), C.c_int64]),
     "ewal_copy_records": (C.c_int64, [vp, C.POINTER(RecordDesc), C.c_int64]),
@@ -301,7 +321,7 @@ def header_symbols(path=HEADER):
     """Every function declared in include/ewal.h."""
     txt = open(path).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit)_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg)_[a-z0-9_]+)\s*\(", txt)))
 
 
 def status_string(st):

@@ -31,6 +31,7 @@
 #include "frame_fields.hip"
 #include "frame_kernels.hip"
 #include "snap_save.hip"
+#include "msg_encode.hip"
 #include "ewal_stage.h"
 #include "ewal_wire.h"
 
@@ -179,6 +180,9 @@ struct ewal_ctx {
   // batched raftpb.Message decode (emsg_decode_batch_device)
   DevBuf moff, mlen, mcnt, mfirst, mout, ments, mscnt, msfirst, msegs;
   uint64_t mtotal = 0, mstotal = 0;
+  // batched raftpb.Message encode (emsg_encode_batch_device): sizes, their
+  // exclusive sums, the per-message {off, len}
+  DevBuf menc;
   std::vector<uint64_t> bent_first, bnents;   // per shard: first ent in bents, count
   std::vector<std::vector<ewal_unrec>> bunrec;       // per shard replayed alone: its XXX_unrecognized side list
   std::vector<std::vector<uint8_t>> bunrec_bytes;
@@ -3227,6 +3231,90 @@ int64_t emsg_copy_entries(ewal_ctx *c, uint64_t first, ewal_entry *out, int64_t 
     EW_CHECK(hipStreamSynchronize(c->stream));
   }
   return n;
+}
+
+uint32_t emsg_encode_tile_bytes(void) { return EME_TILE; }
+
+static_assert(EME_TILE % 16 == 0 && sizeof(emsg_out) == 144 && sizeof(emsg_encoded) == 16, "emsg_encode layout");
+int emsg_encode_batch_device(ewal_ctx *c, const void *d_data, uint64_t data_len_total, const emsg_out *d_msgs,
+                             uint64_t n, const ewal_entry *d_ents, uint64_t n_ents_total, const uint64_t *d_u64,
+                             uint64_t n_u64, void *d_out, uint64_t cap, emsg_encoded *h_out, uint64_t *out_len) {
+  if (!c || !out_len || (n && !d_msgs) || (n_ents_total && !d_ents) || (n_u64 && !d_u64) ||
+      (data_len_total && !d_data))
+    return EWAL_E_INVAL;
+  *out_len = 0;
+  if ((((uintptr_t)d_data | (uintptr_t)d_out) & 15) != 0) return EWAL_E_INVAL;
+  if (n >= 0x7fffffffull || n_ents_total >= 0x7fffffffull || n_u64 >= 0x7fffffffull) return EWAL_E_INVAL;
+  const uintptr_t pd = (uintptr_t)d_data, po = (uintptr_t)d_out;
+  if (pd + data_len_total < pd || (d_out && po + cap < po)) return EWAL_E_INVAL;
+  if (d_out && data_len_total && cap && pd < po + cap && po < pd + data_len_total) return EWAL_E_INVAL;
+  if (n == 0) return EWAL_OK;
+  EW_CHECK(hipSetDevice(c->device));
+  forget_records(c);
+  EW_CHECK(c->small.ensure(sizeof(Small)));
+  Small *ds = c->small.as<Small>();
+  EW_CHECK(hipMemsetAsync(&ds->errflag, 0, 4, c->stream));
+  // scratch: fsz, X (n_ents_total + 1), usz, NX (n_u64 + 1), msz, moff (n + 1), enc (n)
+  const uint64_t ne1 = n_ents_total + 1, nu1 = n_u64 + 1, n1 = n + 1;
+  EW_CHECK(c->menc.ensure((size_t)(2 * (ne1 + nu1 + n1) * 8 + n * sizeof(emsg_encoded))));
+  uint64_t *fsz = c->menc.as<uint64_t>(), *X = fsz + ne1, *usz = X + ne1, *NX = usz + nu1, *msz = NX + nu1,
+           *moff = msz + n1;
+  emsg_encoded *enc = (emsg_encoded *)(moff + n1);
+  EW_CHECK(hipEventRecord(c->ev0, c->stream));
+  hipLaunchKernelGGL(k_menc_esz, dim3(grid_for(ne1, 256)), dim3(256), 0, c->stream, d_ents, n_ents_total,
+                     data_len_total, fsz, &ds->errflag);
+  hipLaunchKernelGGL(k_menc_usz, dim3(grid_for(nu1, 256)), dim3(256), 0, c->stream, d_u64, n_u64, usz);
+  size_t tb = 0, tb1 = 0;
+  EW_CHECK(hipcub::DeviceScan::ExclusiveScan(nullptr, tb1, fsz, X, EmeSatAdd(), (uint64_t)0, (int)ne1, c->stream));
+  tb = std::max(tb, tb1);
+  EW_CHECK(hipcub::DeviceScan::ExclusiveScan(nullptr, tb1, usz, NX, EmeSatAdd(), (uint64_t)0, (int)nu1, c->stream));
+  tb = std::max(tb, tb1);
+  EW_CHECK(hipcub::DeviceScan::ExclusiveScan(nullptr, tb1, msz, moff, EmeSatAdd(), (uint64_t)0, (int)n1, c->stream));
+  tb = std::max(tb, tb1);
+  EW_CHECK(c->tmp.ensure(tb));
+  EW_CHECK(hipcub::DeviceScan::ExclusiveScan(c->tmp.p, tb, fsz, X, EmeSatAdd(), (uint64_t)0, (int)ne1, c->stream));
+  EW_CHECK(hipcub::DeviceScan::ExclusiveScan(c->tmp.p, tb, usz, NX, EmeSatAdd(), (uint64_t)0, (int)nu1, c->stream));
+  hipLaunchKernelGGL(k_menc_msz, dim3(grid_for(n1, 256)), dim3(256), 0, c->stream, d_msgs, n, n_ents_total, n_u64,
+                     data_len_total, (const uint64_t *)X, (const uint64_t *)NX, msz, &ds->errflag);
+  EW_CHECK(hipcub::DeviceScan::ExclusiveScan(c->tmp.p, tb, msz, moff, EmeSatAdd(), (uint64_t)0, (int)n1, c->stream));
+  hipLaunchKernelGGL(k_menc_pack, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, (const uint64_t *)moff, n, enc);
+  EW_CHECK(hipGetLastError());
+  // the one decision point: error flag and total (a failed range check left
+  // sizes of 0 behind, so h_out is only meaningful when the call succeeds)
+  uint32_t bad = 0;
+  uint64_t total = 0;
+  EW_CHECK(hipMemcpyAsync(&bad, &ds->errflag, 4, hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipMemcpyAsync(&total, moff + n, 8, hipMemcpyDeviceToHost, c->stream));
+  if (h_out) EW_CHECK(hipMemcpyAsync(h_out, enc, (size_t)n * sizeof(emsg_encoded), hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  if (bad) return EWAL_E_INVAL;
+  if (total == ~0ull) return EWAL_E_NOMEM;   // more than 64 bits: more than any cap
+  if (!d_out) {
+    *out_len = total;
+    return EWAL_OK;
+  }
+  if (total > cap) return EWAL_E_NOMEM;
+  EmeArgs a;
+  a.data = (const uint8_t *)d_data;
+  a.data_len = data_len_total;
+  a.msgs = d_msgs;
+  a.n = n;
+  a.ents = d_ents;
+  a.u64 = d_u64;
+  a.X = X;
+  a.NX = NX;
+  a.moff = moff;
+  a.out = (uint8_t *)d_out;
+  a.total = total;
+  const uint64_t ntiles = (total + EME_TILE - 1) / EME_TILE;
+  const unsigned grid =
+      (unsigned)std::min<uint64_t>(grid_for(ntiles, EME_WAVES), (uint64_t)std::max(1, c->num_cu) * (16 / EME_WAVES));   // 4 waves per SIMD fit
+  hipLaunchKernelGGL(k_menc_body, dim3(grid), dim3(64 * EME_WAVES), 0, c->stream, a);
+  EW_CHECK(hipGetLastError());
+  EW_CHECK(hipEventRecord(c->ev1, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  *out_len = total;
+  return EWAL_OK;
 }
 
 float ewal_last_device_ms(ewal_ctx *c) {

@@ -663,6 +663,41 @@ uint64_t esnap_save_bound(const esnap_save_rec *recs, uint32_t n, const uint64_t
   return tot;
 }
 
+// ---- raftpb.Message.Size, raft/raftpb/raft.pb.go:849-872 --------------------
+uint32_t emsg_out_size(void) { return (uint32_t)sizeof(emsg_out); }
+uint32_t emsg_encoded_size(void) { return (uint32_t)sizeof(emsg_encoded); }
+
+uint64_t emsg_encode_size(const emsg_out *h_msgs, uint64_t n, const ewal_entry *h_ents, uint64_t n_ents_total,
+                          const uint64_t *h_u64, uint64_t n_u64) {
+  using ewal_wire::sov;
+  uint64_t tot = 0, e;
+  for (uint64_t i = 0; i < n; ++i) {
+    const emsg_out &m = h_msgs[i];
+    if (__builtin_add_overflow(m.ents_first, m.n_ents, &e) || e > n_ents_total ||
+        __builtin_add_overflow(m.snap_nodes_off, m.snap_n_nodes, &e) || e > n_u64 ||
+        __builtin_add_overflow(m.snap_removed_off, m.snap_n_removed, &e) || e > n_u64)
+      return ~0ull;
+    uint64_t s = 1 + sov(m.snap_data_len) + 1 + sov(m.snap_index) + 1 + sov(m.snap_term);   // Snapshot.Size()
+    if (__builtin_add_overflow(s, m.snap_data_len, &s)) return ~0ull;
+    for (uint64_t k = 0; k < m.snap_n_nodes; ++k)
+      if (__builtin_add_overflow(s, (uint64_t)(1 + sov(h_u64[m.snap_nodes_off + k])), &s)) return ~0ull;
+    for (uint64_t k = 0; k < m.snap_n_removed; ++k)
+      if (__builtin_add_overflow(s, (uint64_t)(1 + sov(h_u64[m.snap_removed_off + k])), &s)) return ~0ull;
+    uint64_t z = 6 + sov(m.type) + sov(m.to) + sov(m.from) + sov(m.term) + sov(m.log_term) + sov(m.index) + 1 +
+                 sov(m.commit) + 1 + sov(s) + 2;
+    if (__builtin_add_overflow(z, s, &z)) return ~0ull;
+    for (uint64_t k = 0; k < m.n_ents; ++k) {
+      const ewal_entry &en = h_ents[m.ents_first + k];
+      uint64_t l = 4 + sov((uint64_t)(int64_t)en.type) + sov(en.term) + sov(en.index) + sov(en.data_len);
+      if (__builtin_add_overflow(l, en.data_len, &l) || __builtin_add_overflow(z, l, &z) ||
+          __builtin_add_overflow(z, (uint64_t)(1 + sov(l)), &z))
+        return ~0ull;
+    }
+    if (__builtin_add_overflow(tot, z, &tot)) return ~0ull;
+  }
+  return tot;
+}
+
 void esnap_snap_name(uint64_t term, uint64_t index, char *out) {
   std::snprintf(out, 39, "%016llx-%016llx.snap", (unsigned long long)term, (unsigned long long)index);
 }

@@ -1,9 +1,14 @@
-"""raftpb.Message ingress decode on the GPU (emsg_decode_batch_device).
+"""raftpb.Message on the GPU: the /raft ingress decode (emsg_decode_batch_device)
+and the egress encode (emsg_encode_batch_device).
 
 Mirrors `(*raftpb.Message).Unmarshal` (raft/raftpb/raft.pb.go:407-617), the
 call etcdhttp's serveRaft makes for every POST /raft body
 (etcdserver/etcdhttp/http.go:119-146), batched over many bodies.  Results are
-dicts shaped like the oracle's `message_unmarshal` (tests compare them)."""
+dicts shaped like the oracle's `message_unmarshal` (tests compare them).
+
+The encode mirrors `(*raftpb.Message).Marshal` (raft.pb.go:1000-1068), the call
+`send` makes per outgoing message (etcdserver/cluster_store.go:118-144),
+batched over messages whose Entries and Snapshot.Data stay in HBM."""
 import ctypes as C
 
 from . import _lib as L
@@ -101,3 +106,97 @@ def decode_messages(ctx, bodies):
                                   nodes=[g.off for g in bykind.get((L.SEG_SNAP_NODE, -1), [])],
                                   removed=[g.off for g in bykind.get((L.SEG_SNAP_REMOVED, -1), [])])))
     return res
+
+
+# bytes of the output one wave of the encode's body kernel owns (0: an older A/B build, EWAL_LIB_PATH)
+ENCODE_TILE = lib.emsg_encode_tile_bytes() if hasattr(lib, "emsg_encode_tile_bytes") else 0
+
+
+def _ptr(d):
+    """A device pointer argument: None, a DeviceBuffer, a c_void_p or an int."""
+    if d is None:
+        return None
+    if hasattr(d, "ptr"):
+        d = d.ptr
+    return d if isinstance(d, C.c_void_p) else C.c_void_p(d)
+
+
+def encode_messages_device(ctx, d_data, data_len, d_msgs, n, d_ents, n_ents, d_u64, n_u64, d_out, cap):
+    """emsg_encode_batch_device over device arrays (emsg_out[n], ewal_entry[n_ents],
+    uint64[n_u64]; Data ranges index d_data[0, data_len)): message i is
+    d_out[offs[i], offs[i] + lens[i]).  Returns (offs, lens, total); with
+    d_out=None it is the size query and nothing is written."""
+    enc = (L.Encoded * max(n, 1))()
+    total = C.c_uint64(0)
+    check(lib.emsg_encode_batch_device(ctx.handle, _ptr(d_data), data_len, _ptr(d_msgs), n, _ptr(d_ents), n_ents,
+                                       _ptr(d_u64), n_u64, _ptr(d_out), cap, enc, C.byref(total)))
+    return [e.off for e in enc[:n]], [e.len for e in enc[:n]], total.value
+
+
+def pack_messages(msgs):
+    """Host arrays for a list of message dicts shaped like decode_messages'
+    results (type, to, from_, term, log_term, index, commit, reject, ents:
+    [type, term, index, data], snap: data, index, term, nodes, removed; all
+    optional): (data blob, emsg_out[], ewal_entry[], uint64[]) and their
+    counts n_ents, n_u64."""
+    blob, u64, ents = bytearray(), [], []
+    out = (L.OutMsg * max(len(msgs), 1))()
+    for o, m in zip(out, msgs):
+        o.type, o.to, o.from_, o.term = m.get("type", 0), m.get("to", 0), m.get("from_", 0), m.get("term", 0)
+        o.log_term, o.index, o.commit = m.get("log_term", 0), m.get("index", 0), m.get("commit", 0)
+        o.reject = 1 if m.get("reject") else 0
+        es = m.get("ents") or ()
+        o.ents_first, o.n_ents = len(ents), len(es)
+        for e in es:
+            d = e.get("data")
+            ents.append((e.get("term", 0), e.get("index", 0), len(blob) if d else 0, len(d) if d else 0,
+                         e.get("type", 0), 1 if d is None else 0))
+            blob += d or b""
+        sn = m.get("snap") or {}
+        d = sn.get("data") or b""
+        o.snap_index, o.snap_term = sn.get("index", 0), sn.get("term", 0)
+        o.snap_data_off, o.snap_data_len = (len(blob) if d else 0), len(d)
+        blob += d
+        nodes, removed = list(sn.get("nodes") or ()), list(sn.get("removed") or ())
+        o.snap_nodes_off, o.snap_n_nodes = len(u64), len(nodes)
+        u64 += nodes
+        o.snap_removed_off, o.snap_n_removed = len(u64), len(removed)
+        u64 += removed
+    earr = (L.EntryDesc * max(len(ents), 1))()
+    for a, (term, index, off, ln, type_, nil) in zip(earr, ents):
+        a.term, a.index, a.data_off, a.data_len, a.type, a.data_nil = term, index, off, ln, type_, nil
+    return bytes(blob), out, earr, len(ents), (C.c_uint64 * max(len(u64), 1))(*u64), len(u64)
+
+
+def encode_size(msgs):
+    """emsg_encode_size: the summed Message.Size() of the message dicts (host only)."""
+    _, out, earr, ne, u64, nu = pack_messages(msgs)
+    return lib.emsg_encode_size(out, len(msgs), earr, ne, u64, nu)
+
+
+def _up(ctx, raw):
+    d = ctx.alloc(len(raw) + 64)
+    if raw:
+        d.upload(raw)
+    return d
+
+
+def encode_messages(ctx, msgs):
+    """Marshal message dicts (host bytes) on the GPU: uploads the payload and
+    the descriptors, encodes, downloads; one `bytes` per message."""
+    n = len(msgs)
+    if n == 0:
+        return []
+    blob, out, earr, ne, u64, nu = pack_messages(msgs)
+    bufs = [_up(ctx, blob), _up(ctx, C.string_at(out, n * C.sizeof(L.OutMsg))),
+            _up(ctx, C.string_at(earr, ne * C.sizeof(L.EntryDesc))), _up(ctx, C.string_at(u64, nu * 8))]
+    try:
+        args = (ctx, bufs[0], len(blob), bufs[1], n, bufs[2], ne, bufs[3], nu)
+        _, _, total = encode_messages_device(*args, None, 0)
+        bufs.append(ctx.alloc(total + 64))
+        offs, lens, total = encode_messages_device(*args, bufs[4], total)
+        raw = bufs[4].download(total)
+    finally:
+        for b in bufs:
+            b.free()
+    return [raw[o:o + k] for o, k in zip(offs, lens)]

@@ -748,6 +748,64 @@ int emsg_decode_batch_device(ewal_ctx *ctx, const void *d_buf, uint64_t buf_len,
 int64_t emsg_copy_entries(ewal_ctx *ctx, uint64_t first, ewal_entry *out, int64_t cap);
 int64_t emsg_copy_segments(ewal_ctx *ctx, uint64_t first, emsg_segment *out, int64_t cap);
 
+/* ---- raft egress: raftpb.Message.Marshal, raft/raftpb/raft.pb.go:849-872,
+ * 1000-1068 (called per outgoing message by send,
+ * etcdserver/cluster_store.go:118-144), batched over n messages whose payload
+ * is resident in HBM.  One emsg_out per message (a DEVICE array): */
+typedef struct emsg_out {
+  uint64_t type, to, from, term, log_term, index, commit;  /* uint64(m.Type) etc., as MarshalTo casts them */
+  uint64_t ents_first, n_ents;       /* Entries = d_ents[ents_first, ents_first + n_ents) */
+  uint64_t snap_index, snap_term;
+  uint64_t snap_data_off, snap_data_len;     /* Snapshot.Data, a range of d_data */
+  uint64_t snap_nodes_off, snap_n_nodes;     /* Snapshot.Nodes, a range of d_u64 (uint64 units) */
+  uint64_t snap_removed_off, snap_n_removed; /* Snapshot.RemovedNodes, likewise */
+  int32_t reject, pad;
+} emsg_out;                                   /* 144 bytes */
+typedef struct emsg_encoded { uint64_t off, len; } emsg_encoded;
+/* Message i becomes d_out[h_out[i].off, + h_out[i].len), byte-identical to
+ * (*Message).Marshal() with its nested Entry.MarshalTo (raft.pb.go:921-943:
+ * field 4 always written, Type sign-extended as uint64(int32)) and
+ * Snapshot.MarshalTo (:954-999: field 9 always written with a real body, so
+ * Message{} is 24 bytes).  An entry's Data is d_data[data_off, + data_len)
+ * (ewal_entry, as ReadAll, the write path and emsg_decode_batch_device return
+ * them).  The messages are packed back to back in order of i, off[0] == 0;
+ * *out_len is their sum and no byte of d_out at or past it is written, so
+ * d_out with h_out's offs and lens feeds emsg_decode_batch_device directly.
+ * The entry ranges (and the Data, Nodes, RemovedNodes ranges) of different
+ * messages may coincide or overlap: a leader's fan-out shares one range
+ * among its followers' messages.
+ * d_out == NULL is a size query: h_out (nullable) and *out_len are filled,
+ * nothing is written.  n == 0: EWAL_OK, *out_len = 0.
+ * Errors, all decided before any byte of d_out is written:
+ *   EWAL_E_INVAL  an entry range outside n_ents_total; a Data, Nodes or
+ *                 RemovedNodes range outside its array, or one that wraps
+ *                 (every entry of d_ents and every message is checked); an
+ *                 entry with data_nil == 2 (its Data is not in d_data);
+ *                 d_data or d_out not 16-byte aligned; d_out overlapping
+ *                 d_data; n, n_ents_total or n_u64 >= 2^31 - 1; entry or
+ *                 node sizes whose sum does not fit 64 bits
+ *   EWAL_E_NOMEM  the total is greater than cap
+ * A compute call on the ctx (it invalidates ewal_copy_records like the
+ * others) that runs on the ctx's stream (ewal_ctx_set_stream); a repeated
+ * call of the same or a smaller shape allocates nothing.
+ * XXX_unrecognized of Message, Entry and Snapshot is not encoded: etcd's own
+ * encoder never produces it and ewal_entry has no place for it. */
+int emsg_encode_batch_device(ewal_ctx *ctx, const void *d_data, uint64_t data_len_total,
+                             const emsg_out *d_msgs, uint64_t n,
+                             const ewal_entry *d_ents, uint64_t n_ents_total,
+                             const uint64_t *d_u64, uint64_t n_u64,
+                             void *d_out, uint64_t cap,
+                             emsg_encoded *h_out /* host, n, nullable */, uint64_t *out_len);
+/* Host only: the exact sum of Message.Size() over host copies of the same
+ * arrays; ~0 when it does not fit 64 bits or a range lies outside its array. */
+uint64_t emsg_encode_size(const emsg_out *h_msgs, uint64_t n, const ewal_entry *h_ents, uint64_t n_ents_total,
+                          const uint64_t *h_u64, uint64_t n_u64);
+/* For bindings / tests: the bytes of d_out one wave of the body kernel owns,
+ * sizeof(emsg_out), sizeof(emsg_encoded). */
+uint32_t emsg_encode_tile_bytes(void);
+uint32_t emsg_out_size(void);
+uint32_t emsg_encoded_size(void);
+
 #ifdef __cplusplus
 }
 #endif
