@@ -50,6 +50,7 @@ PANIC_ENTRY = 34
 PANIC_STATE = 35
 PANIC_INDEX_GAP = 36
 NONTERMINATING = 37
+PANIC_COMMITTED_CONFLICT = 38
 UNSUPPORTED_ENCODING = 48
 E_HIP, E_INVAL, E_NOMEM, E_NODEVICE, E_TIMEOUT, E_IO = -1, -2, -3, -4, -5, -6
 
@@ -89,6 +90,23 @@ class OutMsg(C.Structure):   # emsg_out
 
 class Encoded(C.Structure):   # emsg_encoded
     _fields_ = [("off", C.c_uint64), ("len", C.c_uint64)]
+
+
+class LogGroup(C.Structure):   # elog_group
+    _fields_ = [("id", C.c_uint64), ("term", C.c_uint64), ("committed", C.c_uint64), ("unstable", C.c_uint64),
+                ("log_offset", C.c_uint64), ("nlog", C.c_uint64), ("terms_off", C.c_uint64),
+                ("terms_cap", C.c_uint64)]
+
+
+class LogApp(C.Structure):   # elog_app
+    _fields_ = [("group", C.c_uint64), ("from_", C.c_uint64), ("index", C.c_uint64), ("log_term", C.c_uint64),
+                ("commit", C.c_uint64), ("ents_first", C.c_uint64), ("n_ents", C.c_uint64), ("pad", C.c_uint64)]
+
+
+class LogAppResult(C.Structure):   # elog_app_result
+    _fields_ = [("status", C.c_int32), ("accepted", C.c_int32), ("conflict", C.c_uint64),
+                ("app_first", C.c_uint64), ("n_app", C.c_uint64), ("last_index", C.c_uint64),
+                ("committed", C.c_uint64)]
 
 
 SNAP_FIELD_DATA, SNAP_FIELD_UNREC, SNAP_FIELD_NODES, SNAP_FIELD_REMOVED = range(4)
@@ -290,6 +308,12 @@ _SIGS = {
     "esnap_saved_size": (C.c_uint32, []),
     "ecommit_batch_device": (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]),
     "ecommit_batch_rec_device": (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]),
+    "elog_append_batch_device": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, vp,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "elog_group_size": (C.c_uint32, []),
+    "elog_app_size": (C.c_uint32, []),
+    "elog_app_result_size": (C.c_uint32, []),
+    "elog_lane_max_entries": (C.c_uint32, []),
 }
 for _name, (_res, _args) in _SIGS.items():
     if os.environ.get("EWAL_LIB_PATH") and not hasattr(lib, _name):
@@ -321,7 +345,7 @@ def header_symbols(path=HEADER):
     """Every function declared in include/ewal.h."""
     txt = open(path).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg)_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log)_[a-z0-9_]+)\s*\(", txt)))
 
 
 def status_string(st):
@@ -352,6 +376,6 @@ def check(st, detail=0, record=-1, offset=-1):
         return
     if st == E_NODEVICE:
         raise NoDeviceError(st)
-    if 32 <= st <= 37:
+    if 32 <= st <= 38:
         raise GoPanic(st, detail, record, offset)
     raise EwalError(st, detail, record, offset)

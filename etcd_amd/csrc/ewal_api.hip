@@ -32,6 +32,7 @@
 #include "frame_kernels.hip"
 #include "snap_save.hip"
 #include "msg_encode.hip"
+#include "log_append.hip"
 #include "ewal_stage.h"
 #include "ewal_wire.h"
 
@@ -183,6 +184,9 @@ struct ewal_ctx {
   // batched raftpb.Message encode (emsg_encode_batch_device): sizes, their
   // exclusive sums, the per-message {off, len}
   DevBuf menc;
+  // batched follower append (elog_append_batch_device): head words, the
+  // groups' claims, the long messages' work list, per-workgroup partial sums
+  DevBuf lapp;
   std::vector<uint64_t> bent_first, bnents;   // per shard: first ent in bents, count
   std::vector<std::vector<ewal_unrec>> bunrec;       // per shard replayed alone: its XXX_unrecognized side list
   std::vector<std::vector<uint8_t>> bunrec_bytes;
@@ -3370,6 +3374,77 @@ int ecommit_batch_rec_device(ewal_ctx *c, uint64_t G, const ecommit_group *group
     EW_CHECK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     *device_ms = ms;
   }
+  return EWAL_OK;
+}
+
+uint32_t elog_group_size(void) { return sizeof(elog_group); }
+uint32_t elog_app_size(void) { return sizeof(elog_app); }
+uint32_t elog_app_result_size(void) { return sizeof(elog_app_result); }
+uint32_t elog_lane_max_entries(void) { return ELOG_LANE_MAX; }
+
+static_assert(sizeof(elog_group) == 64 && sizeof(elog_app) == 64 && sizeof(elog_app_result) == 48 &&
+                  sizeof(ewal_entry) == 40 && offsetof(emsg_out, reject) == 136,
+              "elog_append layout");
+int elog_append_batch_device(ewal_ctx *c, elog_group *d_groups, uint64_t G, uint64_t *d_terms, uint64_t n_terms,
+                             const elog_app *d_apps, uint64_t n, const ewal_entry *d_ents, uint64_t n_ents_total,
+                             elog_app_result *d_res, emsg_out *d_resp, uint64_t *n_accepted, uint64_t *n_appended) {
+  if (n_accepted) *n_accepted = 0;
+  if (n_appended) *n_appended = 0;
+  if (!c) return EWAL_E_INVAL;
+  if (n >= 0x7fffffffull || G >= 0x7fffffffull) return EWAL_E_INVAL;
+  if (n == 0) return EWAL_OK;
+  if (!d_groups || !d_apps || !d_res || (n_terms && !d_terms) || (n_ents_total && !d_ents)) return EWAL_E_INVAL;
+  if ((((uintptr_t)d_groups | (uintptr_t)d_apps | (uintptr_t)d_res | (uintptr_t)d_resp) & 15) != 0 ||
+      ((uintptr_t)d_terms & 7) != 0 || ((uintptr_t)d_ents & 7) != 0)
+    return EWAL_E_INVAL;
+  EW_CHECK(hipSetDevice(c->device));
+  forget_records(c);
+  // scratch: head | claim[G] | wlist[n] | partial[2 * (lane workgroups + wave workgroups)]
+  const uint32_t lane_blocks = grid_for(n, 256);
+  const uint32_t wave_blocks_max =
+      (uint32_t)std::min<uint64_t>(grid_for(n, 4), (uint64_t)std::max(1, c->num_cu) * 8);   // 32 waves a CU
+  const size_t o_claim = 64, o_wlist = (o_claim + (size_t)G * 4 + 15) & ~(size_t)15,
+               o_part = (o_wlist + (size_t)n * 4 + 15) & ~(size_t)15;
+  EW_CHECK(c->lapp.ensure(o_part + ((size_t)lane_blocks + wave_blocks_max) * 16));
+  uint8_t *base = c->lapp.as<uint8_t>();
+  ElogArgs a;
+  a.groups = d_groups;
+  a.G = G;
+  a.terms = d_terms;
+  a.n_terms = n_terms;
+  a.apps = d_apps;
+  a.n = n;
+  a.ents = d_ents;
+  a.n_ents_total = n_ents_total;
+  a.res = d_res;
+  a.resp = d_resp;
+  a.head = (ElogHead *)base;
+  a.claim = (uint32_t *)(base + o_claim);
+  a.wlist = (uint32_t *)(base + o_wlist);
+  a.partial = (unsigned long long *)(base + o_part);
+  a.lane_blocks = lane_blocks;
+  EW_CHECK(hipEventRecord(c->ev0, c->stream));
+  EW_CHECK(hipMemsetAsync(a.head, 0, sizeof(ElogHead), c->stream));
+  if (G) EW_CHECK(hipMemsetAsync(a.claim, 0xff, (size_t)G * 4, c->stream));
+  hipLaunchKernelGGL(k_lapp_check, dim3(lane_blocks), dim3(256), 0, c->stream, a);
+  EW_CHECK(hipGetLastError());
+  // the one decision point: nothing has been modified yet
+  ElogHead h;
+  EW_CHECK(hipMemcpyAsync(&h, a.head, 8, hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  if (h.errflag & ELOG_ERR_INVAL) return EWAL_E_INVAL;
+  if (h.errflag & ELOG_ERR_NOMEM) return EWAL_E_NOMEM;
+  const uint32_t wave_blocks = std::min<uint32_t>(grid_for(h.nlong, 4), wave_blocks_max);
+  hipLaunchKernelGGL(k_lapp_lane, dim3(lane_blocks), dim3(256), 0, c->stream, a);
+  if (wave_blocks) hipLaunchKernelGGL(k_lapp_wave, dim3(wave_blocks), dim3(256), 0, c->stream, a, h.nlong);
+  hipLaunchKernelGGL(k_lapp_sum, dim3(1), dim3(256), 0, c->stream, (const unsigned long long *)a.partial,
+                     lane_blocks + wave_blocks, a.head);
+  EW_CHECK(hipGetLastError());
+  EW_CHECK(hipEventRecord(c->ev1, c->stream));
+  EW_CHECK(hipMemcpyAsync(&h, a.head, sizeof(ElogHead), hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  if (n_accepted) *n_accepted = h.accepted;
+  if (n_appended) *n_appended = h.appended;
   return EWAL_OK;
 }
 

@@ -318,6 +318,7 @@ const char *ewal_status_string(int st) {
   case EWAL_PANIC_STATE: return "panic: mustUnmarshalState";
   case EWAL_PANIC_INDEX_GAP: return "panic: ents index gap";
   case EWAL_NONTERMINATING: return "reference does not terminate";
+  case EWAL_PANIC_COMMITTED_CONFLICT: return "panic: conflict with committed entry";
   case EWAL_UNSUPPORTED_ENCODING: return "unsupported (non-canonical) record encoding";
   case EWAL_E_HIP: return "HIP error";
   case EWAL_E_INVAL: return "invalid argument";

@@ -44,6 +44,7 @@ enum {
   EWAL_PANIC_STATE = 35,           /* mustUnmarshalState     wal/decoder.go:71-77 */
   EWAL_PANIC_INDEX_GAP = 36,       /* ents[:e.Index-ri] past len wal/wal.go:173 */
   EWAL_NONTERMINATING = 37,        /* the reference never returns */
+  EWAL_PANIC_COMMITTED_CONFLICT = 38, /* panic("conflict with committed entry"), raft/log.go:57 */
   EWAL_UNSUPPORTED_ENCODING = 48,  /* protobuf groups nested deeper than the device
                                       walker's stack; reported, never guessed */
   /* infrastructure (negative) */
@@ -693,6 +694,108 @@ typedef struct ecommit_group {
 int ecommit_batch_rec_device(ewal_ctx *ctx, uint64_t G, const ecommit_group *groups, const uint64_t *log_ptr,
                              const uint64_t *log_terms, uint64_t *committed_out, uint8_t *changed,
                              uint8_t *status, double *device_ms);
+
+/* ---- follower append: raft.handleAppendEntries, raft/raft.go:410-416 -------
+ * Batched over n msgApp for n different raft groups: raftLog.maybeAppend with
+ * matchTerm, findConflict, append, at, isOutOfBounds and lastIndex
+ * (raft/log.go:49-84, 115-117, 141-146, 194-217), then the msgAppResp that
+ * send (raft/raft.go:190-199) queues.  The log of group g is the window
+ * d_terms[terms_off, terms_off + nlog) of entry terms -- the same windows
+ * ecommit_batch_device reads -- with room for terms_cap entries; the entries
+ * of message i are ewal_entry views d_ents[ents_first, + n_ents) as ReadAll
+ * and emsg_decode_batch_device return them.  All arithmetic is Go's uint64
+ * and wraps. */
+/* follower state of one raft group; a DEVICE array of G, updated in place */
+typedef struct elog_group {        /* 64 bytes */
+  uint64_t id;          /* raft.id   -> From of the response (raft.go:190-199) */
+  uint64_t term;        /* raft.Term -> Term of the response                   */
+  uint64_t committed;   /* raftLog.committed                    (updated) */
+  uint64_t unstable;    /* raftLog.unstable                     (updated) */
+  uint64_t log_offset;  /* raftLog.offset: the index of ents[0]           */
+  uint64_t nlog;        /* len(raftLog.ents)                    (updated) */
+  uint64_t terms_off;   /* ents[k].Term == d_terms[terms_off + k], k < nlog */
+  uint64_t terms_cap;   /* room at terms_off, in entries                  */
+} elog_group;
+/* one msgApp; a DEVICE array of n */
+typedef struct elog_app {          /* 64 bytes */
+  uint64_t group;                  /* which elog_group handles it */
+  uint64_t from, index, log_term, commit;   /* m.From, m.Index, m.LogTerm, m.Commit */
+  uint64_t ents_first, n_ents;     /* m.Entries = d_ents[ents_first, +n_ents) (ewal_entry) */
+  uint64_t pad;
+} elog_app;
+/* what happened to message i; a DEVICE array of n */
+typedef struct elog_app_result {   /* 48 bytes */
+  int32_t status;       /* EWAL_OK, EWAL_PANIC_BOUNDS, EWAL_PANIC_COMMITTED_CONFLICT */
+  int32_t accepted;     /* maybeAppend's return (0: the response rejects) */
+  uint64_t conflict;    /* findConflict's ci; 0: none */
+  uint64_t app_first, n_app;   /* the entries appended: d_ents[app_first, +n_app), a suffix
+                                  of the message's range; n_app == 0: nothing appended */
+  uint64_t last_index;  /* raftLog.lastIndex() afterwards */
+  uint64_t committed;   /* raftLog.committed afterwards */
+} elog_app_result;
+/* Per message i (handleAppendEntries exactly), with lastIndex = nlog - 1 +
+ * log_offset, lastnewi = index + n_ents, from = index + 1:
+ *   matchTerm(index, log_term): raftLog.at(index) is nil when index <
+ *     log_offset or index > lastIndex -> the response rejects.  When at passes
+ *     isOutOfBounds but index - log_offset >= nlog Go indexes past ents (only
+ *     possible when nlog - 1 + log_offset wrapped): EWAL_PANIC_BOUNDS.
+ *   findConflict compares terms only, by position from + k (an entry's own
+ *     index field is not looked at); ci = the first position whose log term
+ *     differs or that lies past lastIndex, 0: none -- also when it is 0
+ *     because from + k wrapped.
+ *   0 < ci <= committed: EWAL_PANIC_COMMITTED_CONFLICT.
+ *   accepted with ci > 0: d_terms[terms_off + (ci - log_offset) + j] =
+ *     d_ents[app_first + j].term for j < n_app, nlog = ci - log_offset + n_app,
+ *     unstable = min(unstable, ci).
+ *   every accepted message: committed = max(committed, min(commit, lastnewi)).
+ * A panicking message leaves its group and d_terms unchanged; d_res[i] carries
+ * the status, the unchanged last_index and committed, and 0 elsewhere;
+ * d_resp[i] is 144 zero bytes (Go sends nothing).
+ * No word of d_terms outside [terms_off + ci - log_offset, + n_app) is
+ * written.  Only committed, unstable and nlog of a group that received an
+ * accepted message may change; groups that received no message are not
+ * touched.
+ * d_resp[i] (nullable array) is the msgAppResp after send: type = 4, to =
+ * from, from = group.id, term = group.term, index = lastIndex() after the
+ * append -- or m.Index with reject = 1 --, every other field 0: with the
+ * h_out of a size query d_resp feeds emsg_encode_batch_device unchanged.
+ * Each group handles at most ONE message per call (a second one is a
+ * sequential dependency: the next call).  The term windows of the groups the
+ * messages name must not overlap each other: the caller's contract, not
+ * checked.
+ * Checked on the device before anything is modified (then d_groups, d_terms,
+ * d_res, d_resp are untouched and the counters are 0):
+ *   EWAL_E_INVAL  group >= G; two messages naming the same group; an entry
+ *                 range outside n_ents_total, or one that wraps; terms_off +
+ *                 terms_cap outside n_terms, or wrapping; nlog > terms_cap
+ *                 (INVAL wins over NOMEM when both occur in one call)
+ *   EWAL_E_NOMEM  a message's group has nlog + n_ents > terms_cap (exact
+ *                 enough: an append leaves at most index + 1 - log_offset +
+ *                 n_ents <= nlog + n_ents entries, whatever ci is)
+ * and on the host: EWAL_E_INVAL for a NULL ctx, for d_groups, d_apps, d_res
+ * NULL (or d_terms / d_ents NULL with a non-zero count) while n > 0, for
+ * d_groups, d_apps, d_res, d_resp not 16-byte aligned or d_terms not 8-byte
+ * aligned, and for n or G >= 2^31 - 1.  n == 0: EWAL_OK, counters 0.
+ * *n_accepted = messages accepted, *n_appended = entries appended (both
+ * nullable).  A compute call on the ctx's stream (ewal_ctx_set_stream) like
+ * the others; a repeated call of the same or a smaller shape allocates
+ * nothing. */
+struct emsg_out;
+int elog_append_batch_device(ewal_ctx *ctx, elog_group *d_groups, uint64_t G,
+                             uint64_t *d_terms, uint64_t n_terms,
+                             const elog_app *d_apps, uint64_t n,
+                             const ewal_entry *d_ents, uint64_t n_ents_total,
+                             elog_app_result *d_res,
+                             struct emsg_out *d_resp /* nullable, n; emsg_out is declared below */,
+                             uint64_t *n_accepted, uint64_t *n_appended);
+/* For bindings / tests: sizeof(elog_group), sizeof(elog_app),
+ * sizeof(elog_app_result), and the longest message (in entries) the
+ * lane-per-message kernel takes -- longer ones go to the wave-per-message
+ * kernel. */
+uint32_t elog_group_size(void);
+uint32_t elog_app_size(void);
+uint32_t elog_app_result_size(void);
+uint32_t elog_lane_max_entries(void);
 
 /* ---- raft ingress: raftpb.Message.Unmarshal, raft/raftpb/raft.pb.go:407-617
  * (called per POST /raft in etcdserver/etcdhttp/http.go:119-146), batched
