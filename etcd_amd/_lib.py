@@ -51,6 +51,9 @@ PANIC_STATE = 35
 PANIC_INDEX_GAP = 36
 NONTERMINATING = 37
 PANIC_COMMITTED_CONFLICT = 38
+PANIC_NIL_PROGRESS = 39
+PANIC_NEED_SNAPSHOT = 40
+PANIC_FIRST_ENTRY = 41
 UNSUPPORTED_ENCODING = 48
 E_HIP, E_INVAL, E_NOMEM, E_NODEVICE, E_TIMEOUT, E_IO = -1, -2, -3, -4, -5, -6
 
@@ -108,6 +111,33 @@ class LogAppResult(C.Structure):   # elog_app_result
                 ("app_first", C.c_uint64), ("n_app", C.c_uint64), ("last_index", C.c_uint64),
                 ("committed", C.c_uint64)]
 
+
+class LeadGroup(C.Structure):   # elead_group
+    _fields_ = [("id", C.c_uint64), ("term", C.c_uint64), ("committed", C.c_uint64), ("log_offset", C.c_uint64),
+                ("nlog", C.c_uint64), ("ents_first", C.c_uint64), ("n_peers", C.c_uint64),
+                ("peer_id", C.c_uint64 * 7), ("match", C.c_uint64 * 7), ("next", C.c_uint64 * 7),
+                ("reserved", C.c_uint64 * 4)]
+
+
+class LeadSnap(C.Structure):   # elead_snap
+    _fields_ = [("index", C.c_uint64), ("term", C.c_uint64), ("data_off", C.c_uint64), ("data_len", C.c_uint64),
+                ("nodes_off", C.c_uint64), ("n_nodes", C.c_uint64), ("removed_off", C.c_uint64),
+                ("n_removed", C.c_uint64)]
+
+
+class LeadResp(C.Structure):   # elead_resp
+    _fields_ = [("group", C.c_uint64), ("from_", C.c_uint64), ("term", C.c_uint64), ("index", C.c_uint64),
+                ("reject", C.c_int32), ("pad", C.c_int32), ("pad2", C.c_uint64)]
+
+
+class LeadResult(C.Structure):   # elead_result
+    _fields_ = [("status", C.c_int32), ("action", C.c_int32), ("msg_first", C.c_uint64), ("n_msgs", C.c_uint64),
+                ("committed", C.c_uint64), ("match", C.c_uint64), ("next", C.c_uint64)]
+
+
+# elead_result.action
+(LEAD_NOT_STEPPED, LEAD_IGNORED, LEAD_STEP_DOWN, LEAD_STALE, LEAD_PROBE, LEAD_UPDATED, LEAD_COMMITTED,
+ LEAD_PANICKED) = range(8)
 
 SNAP_FIELD_DATA, SNAP_FIELD_UNREC, SNAP_FIELD_NODES, SNAP_FIELD_REMOVED = range(4)
 SEG_UNREC, SEG_ENTRY_UNREC, SEG_ENTRY_DATA, SEG_SNAP_UNREC, SEG_SNAP_DATA, SEG_SNAP_NODE, SEG_SNAP_REMOVED = range(7)
@@ -314,6 +344,12 @@ _SIGS = {
     "elog_app_size": (C.c_uint32, []),
     "elog_app_result_size": (C.c_uint32, []),
     "elog_lane_max_entries": (C.c_uint32, []),
+    "elead_step_batch_device": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64,
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "elead_group_size": (C.c_uint32, []),
+    "elead_snap_size": (C.c_uint32, []),
+    "elead_resp_size": (C.c_uint32, []),
+    "elead_result_size": (C.c_uint32, []),
 }
 for _name, (_res, _args) in _SIGS.items():
     if os.environ.get("EWAL_LIB_PATH") and not hasattr(lib, _name):
@@ -345,7 +381,7 @@ def header_symbols(path=HEADER):
     """Every function declared in include/ewal.h."""
     txt = open(path).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log)_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead)_[a-z0-9_]+)\s*\(", txt)))
 
 
 def status_string(st):
@@ -376,6 +412,6 @@ def check(st, detail=0, record=-1, offset=-1):
         return
     if st == E_NODEVICE:
         raise NoDeviceError(st)
-    if 32 <= st <= 38:
+    if 32 <= st <= 41:
         raise GoPanic(st, detail, record, offset)
     raise EwalError(st, detail, record, offset)

@@ -33,6 +33,7 @@
 #include "snap_save.hip"
 #include "msg_encode.hip"
 #include "log_append.hip"
+#include "lead_step.hip"
 #include "ewal_stage.h"
 #include "ewal_wire.h"
 
@@ -187,6 +188,9 @@ struct ewal_ctx {
   // batched follower append (elog_append_batch_device): head words, the
   // groups' claims, the long messages' work list, per-workgroup partial sums
   DevBuf lapp;
+  // batched leader msgAppResp step (elead_step_batch_device): head words, the
+  // groups' claims, the runs' message counts, per-workgroup partial sums
+  DevBuf lead;
   std::vector<uint64_t> bent_first, bnents;   // per shard: first ent in bents, count
   std::vector<std::vector<ewal_unrec>> bunrec;       // per shard replayed alone: its XXX_unrecognized side list
   std::vector<std::vector<uint8_t>> bunrec_bytes;
@@ -3445,6 +3449,74 @@ int elog_append_batch_device(ewal_ctx *c, elog_group *d_groups, uint64_t G, uint
   EW_CHECK(hipStreamSynchronize(c->stream));
   if (n_accepted) *n_accepted = h.accepted;
   if (n_appended) *n_appended = h.appended;
+  return EWAL_OK;
+}
+
+uint32_t elead_group_size(void) { return sizeof(elead_group); }
+uint32_t elead_snap_size(void) { return sizeof(elead_snap); }
+uint32_t elead_resp_size(void) { return sizeof(elead_resp); }
+uint32_t elead_result_size(void) { return sizeof(elead_result); }
+
+static_assert(sizeof(elead_group) == 256 && sizeof(elead_snap) == 64 && sizeof(elead_resp) == 48 &&
+                  sizeof(elead_result) == 48 && offsetof(elead_group, match) == 112 &&
+                  offsetof(elead_group, reserved) == 224 && offsetof(emsg_out, snap_index) == 72,
+              "elead_step layout");
+int elead_step_batch_device(ewal_ctx *c, elead_group *d_groups, uint64_t G, const elead_snap *d_snaps,
+                            const ewal_entry *d_ents, uint64_t n_ents_total, const elead_resp *d_resps, uint64_t n,
+                            elead_result *d_res, emsg_out *d_msgs, uint64_t msgs_cap, uint64_t *n_msgs,
+                            uint64_t *n_committed) {
+  if (n_msgs) *n_msgs = 0;
+  if (n_committed) *n_committed = 0;
+  if (!c) return EWAL_E_INVAL;
+  if (n >= 0x7fffffffull || G >= 0x7fffffffull) return EWAL_E_INVAL;
+  if (n == 0) return EWAL_OK;
+  if (!d_groups || !d_resps || !d_res || (n_ents_total && !d_ents)) return EWAL_E_INVAL;
+  if ((((uintptr_t)d_groups | (uintptr_t)d_snaps | (uintptr_t)d_resps | (uintptr_t)d_res | (uintptr_t)d_msgs) & 15) !=
+          0 ||
+      ((uintptr_t)d_ents & 7) != 0)
+    return EWAL_E_INVAL;
+  EW_CHECK(hipSetDevice(c->device));
+  forget_records(c);
+  // scratch: head | claim[G] | run_msgs[n] | partial[2 * workgroups]
+  const uint32_t blocks = grid_for(n, 256);
+  const size_t o_claim = 64, o_run = (o_claim + (size_t)G * 4 + 15) & ~(size_t)15, o_part = o_run + (size_t)n * 8;
+  EW_CHECK(c->lead.ensure(o_part + (size_t)blocks * 16));
+  uint8_t *base = c->lead.as<uint8_t>();
+  EleadArgs a;
+  a.groups = d_groups;
+  a.G = G;
+  a.snaps = d_snaps;
+  a.ents = d_ents;
+  a.n_ents_total = n_ents_total;
+  a.resps = d_resps;
+  a.n = n;
+  a.res = d_res;
+  a.msgs = d_msgs;
+  a.head = (EleadHead *)base;
+  a.claim = (uint32_t *)(base + o_claim);
+  a.run_msgs = (unsigned long long *)(base + o_run);
+  a.partial = (unsigned long long *)(base + o_part);
+  EW_CHECK(hipEventRecord(c->ev0, c->stream));
+  EW_CHECK(hipMemsetAsync(a.head, 0, sizeof(EleadHead), c->stream));
+  if (G) EW_CHECK(hipMemsetAsync(a.claim, 0xff, (size_t)G * 4, c->stream));
+  hipLaunchKernelGGL(k_lead_count, dim3(blocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.partial, blocks, a.head);
+  EW_CHECK(hipGetLastError());
+  // the one decision point: nothing of the caller's has been modified yet
+  EleadHead h;
+  EW_CHECK(hipMemcpyAsync(&h, a.head, sizeof(EleadHead), hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  if (h.errflag & ELEAD_ERR_INVAL) return EWAL_E_INVAL;
+  if (d_msgs && h.n_msgs > msgs_cap) return EWAL_E_NOMEM;
+  if (d_msgs)
+    hipLaunchKernelGGL(k_lead_apply<true>, dim3(blocks), dim3(256), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(k_lead_apply<false>, dim3(blocks), dim3(256), 0, c->stream, a);
+  EW_CHECK(hipGetLastError());
+  EW_CHECK(hipEventRecord(c->ev1, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  if (n_msgs) *n_msgs = h.n_msgs;
+  if (n_committed) *n_committed = h.n_committed;
   return EWAL_OK;
 }
 

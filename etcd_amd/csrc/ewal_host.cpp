@@ -319,6 +319,9 @@ const char *ewal_status_string(int st) {
   case EWAL_PANIC_INDEX_GAP: return "panic: ents index gap";
   case EWAL_NONTERMINATING: return "reference does not terminate";
   case EWAL_PANIC_COMMITTED_CONFLICT: return "panic: conflict with committed entry";
+  case EWAL_PANIC_NIL_PROGRESS: return "panic: nil progress (message from an unknown peer)";
+  case EWAL_PANIC_NEED_SNAPSHOT: return "panic: need non-empty snapshot";
+  case EWAL_PANIC_FIRST_ENTRY: return "panic: cannot return the first entry in log";
   case EWAL_UNSUPPORTED_ENCODING: return "unsupported (non-canonical) record encoding";
   case EWAL_E_HIP: return "HIP error";
   case EWAL_E_INVAL: return "invalid argument";

@@ -45,6 +45,9 @@ enum {
   EWAL_PANIC_INDEX_GAP = 36,       /* ents[:e.Index-ri] past len wal/wal.go:173 */
   EWAL_NONTERMINATING = 37,        /* the reference never returns */
   EWAL_PANIC_COMMITTED_CONFLICT = 38, /* panic("conflict with committed entry"), raft/log.go:57 */
+  EWAL_PANIC_NIL_PROGRESS = 39,    /* r.prs[m.From] is nil and is dereferenced, raft/raft.go:458,462 */
+  EWAL_PANIC_NEED_SNAPSHOT = 40,   /* panic("need non-empty snapshot"), raft/raft.go:559 */
+  EWAL_PANIC_FIRST_ENTRY = 41,     /* panic("cannot return the first entry in log"), raft/log.go:131 */
   EWAL_UNSUPPORTED_ENCODING = 48,  /* protobuf groups nested deeper than the device
                                       walker's stack; reported, never guessed */
   /* infrastructure (negative) */
@@ -796,6 +799,142 @@ uint32_t elog_group_size(void);
 uint32_t elog_app_size(void);
 uint32_t elog_app_result_size(void);
 uint32_t elog_lane_max_entries(void);
+
+/* ---- leader msgAppResp step: stepLeader's msgAppResp case, raft/raft.go:456-466
+ * Batched over n msgAppResp for the leaders of G raft groups: the term switch
+ * of Step (raft.go:393-405), progress.update / maybeDecrTo (:71-90),
+ * raft.maybeCommit (:248-258 with raft/log.go:148-154) and sendAppend /
+ * bcastAppend (:202-236 with needSnapshot :556-564, send :190-199 and
+ * raftLog.term / entries / at / slice, log.go:119-134, 194-217).  What the
+ * follower append leaves as msgAppResp comes in; progress, commit and the next
+ * fan-out's msgApp / msgSnap, as emsg_out records that
+ * emsg_encode_batch_device takes directly, come out.  The log of group g is
+ * the ewal_entry range d_ents[ents_first, + nlog): only its terms are read (an
+ * entry's own index field is not looked at) and d_ents is never written.  All
+ * arithmetic is Go's uint64 and wraps. */
+/* leader state of one raft group; a DEVICE array of G, updated in place */
+typedef struct elead_group {       /* 256 bytes */
+  uint64_t id, term;               /* raft.id, raft.Term */
+  uint64_t committed;              /* raftLog.committed              (updated) */
+  uint64_t log_offset, nlog;       /* raftLog.offset, len(raftLog.ents) */
+  uint64_t ents_first;             /* raftLog.ents[k] is d_ents[ents_first + k] (ewal_entry) */
+  uint64_t n_peers;                /* len(r.prs), the leader itself included: 0..7 */
+  uint64_t peer_id[7];             /* the keys of r.prs */
+  uint64_t match[7], next[7];      /* Progress.match / .next         (updated) */
+  uint64_t reserved[4];            /* 0 */
+} elead_group;
+/* raftLog.snapshot of group g; read only when a msgSnap is sent.  The fields
+ * mean what the snap_* fields of emsg_out mean. */
+typedef struct elead_snap {        /* 64 bytes */
+  uint64_t index, term, data_off, data_len, nodes_off, n_nodes, removed_off, n_removed;
+} elead_snap;
+/* one msgAppResp; a DEVICE array of n */
+typedef struct elead_resp {        /* 48 bytes */
+  uint64_t group;                  /* which elead_group steps it */
+  uint64_t from, term, index;      /* m.From, m.Term, m.Index */
+  int32_t reject, pad;             /* m.Reject */
+  uint64_t pad2;
+} elead_resp;
+/* what response i did */
+enum {
+  ELEAD_NOT_STEPPED = 0,  /* after a step-down or a panic in its group's run: the caller's to step */
+  ELEAD_IGNORED = 1,      /* 0 < m.Term < r.Term */
+  ELEAD_STEP_DOWN = 2,    /* m.Term > r.Term: becomeFollower is the caller's */
+  ELEAD_STALE = 3,        /* a reject that maybeDecrTo refuses */
+  ELEAD_PROBE = 4,        /* a reject: next decremented, one sendAppend(from) */
+  ELEAD_UPDATED = 5,      /* update(index), maybeCommit false */
+  ELEAD_COMMITTED = 6,    /* update(index), maybeCommit true, bcastAppend */
+  ELEAD_PANICKED = 7      /* Go panics (status says where), or the group is unsupported */
+};
+typedef struct elead_result {      /* 48 bytes; a DEVICE array of n */
+  int32_t status;                  /* EWAL_OK, an EWAL_PANIC_ class, EWAL_UNSUPPORTED_ENCODING */
+  int32_t action;                  /* ELEAD_* */
+  uint64_t msg_first, n_msgs;      /* its messages: d_msgs[msg_first, + n_msgs) */
+  uint64_t committed;              /* raftLog.committed after this response */
+  uint64_t match, next;            /* prs[from] after this response (0, 0 when there is none) */
+} elead_result;
+/* Order.  Responses that name the same group must be adjacent in d_resps; they
+ * are stepped in array order, each one seeing the state the previous one left
+ * (a leader of F followers gets up to F responses a round -- the follower
+ * call takes one message per group, this one a run per group).  A run may be
+ * of any length and lie anywhere in the array.
+ * Per response (Step, then stepLeader's msgAppResp case):
+ *   m.Term == 0 or == group.term: stepped (below).
+ *   m.Term < group.term: ELEAD_IGNORED, nothing else happens.
+ *   m.Term > group.term: ELEAD_STEP_DOWN.  The record is not touched and there
+ *     are no messages: the caller runs becomeFollower (and reset) on the host.
+ *     Every later response of that group in this call is ELEAD_NOT_STEPPED,
+ *     has no effect, and is the caller's to step afterwards.
+ *   removed[m.From] and msgDenied (raft.go:376-387) are the caller's routing
+ *     and are not restated: such messages must not be handed to this call.
+ *   reject != 0: maybeDecrTo(index) is false when match != 0 or next - 1 !=
+ *     index: ELEAD_STALE, no message.  Otherwise next = next - 1, or 1 when
+ *     that is 0: ELEAD_PROBE and one sendAppend(from).
+ *   reject == 0: update(index): match = index, next = index + 1.  Then
+ *     maybeCommit: mci = the q-th largest of the n_peers match values, q =
+ *     n_peers / 2 + 1; when mci > committed and raftLog.term(mci) ==
+ *     group.term, committed = mci: ELEAD_COMMITTED and bcastAppend, one
+ *     sendAppend per peer slot whose peer_id != id, in slot order (Go's map
+ *     order is unspecified; slot order is this library's).  Else ELEAD_UPDATED.
+ * sendAppend(to) writes one emsg_out: to, from = id, term = group.term, index
+ * = next - 1 of that peer, and
+ *   index < log_offset (needSnapshot): type = 7 (msgSnap), the eight snap_*
+ *     fields copied from d_snaps[g], every other field 0;
+ *   otherwise type = 3 (msgApp), log_term = raftLog.term(next - 1) (0 when out
+ *     of bounds), commit = committed, Entries = raftLog.entries(next) =
+ *     slice(next, lastIndex + 1) as ents_first = group.ents_first + (next -
+ *     log_offset) and n_ents; a nil slice is ents_first = n_ents = 0; all
+ *     snapshot fields 0.
+ * Where Go panics the response gets a status:
+ *   EWAL_PANIC_NIL_PROGRESS   from is not among the first n_peers peer_id
+ *   EWAL_PANIC_NEED_SNAPSHOT  needSnapshot with d_snaps[g].term == 0, or
+ *                             d_snaps == NULL
+ *   EWAL_PANIC_FIRST_ENTRY    entries(i) with i == log_offset
+ *   EWAL_PANIC_BOUNDS         at / slice index past ents (only when nlog - 1 +
+ *                             log_offset wrapped)
+ * and a group with n_peers > 7 gives EWAL_UNSUPPORTED_ENCODING in the same
+ * way: reported, never guessed.  Such a response -- wherever it panics, the
+ * k-th message of a broadcast included -- has action ELEAD_PANICKED, emits no
+ * message, leaves the record exactly as it was before that response, reports
+ * the unchanged committed and prs[from], and puts the rest of its group's run
+ * at ELEAD_NOT_STEPPED.  Responses stepped before it keep their effect.
+ * d_res[i].match / next are prs[from] after the response for every action (0,
+ * 0 when from is not a key, or the group is unsupported); msg_first is the
+ * number of messages of the responses before i, also when n_msgs == 0.
+ * Output placement.  The messages are dense and deterministic, ordered by
+ * response, then by peer slot; *n_msgs is their number, *n_committed the
+ * number of ELEAD_COMMITTED responses (both nullable).  No emsg_out at or
+ * past *n_msgs is written; no word of a group that no response names is
+ * written; only committed, match[] and next[] of a named group may change.
+ * d_msgs == NULL is a size query: *n_msgs, *n_committed and d_res (msg_first
+ * and n_msgs included) are filled and no group is modified.
+ * Checked on the device before anything is modified (then d_groups, d_res and
+ * d_msgs are untouched and the counters are 0):
+ *   EWAL_E_INVAL  group >= G; a group's responses not adjacent; ents_first +
+ *                 nlog outside n_ents_total, or wrapping; two equal peer_id
+ *                 within the first min(n_peers, 7) slots of a named group;
+ *                 reserved != 0 in a named group
+ *   EWAL_E_NOMEM  the number of messages is greater than msgs_cap (INVAL wins
+ *                 when both occur in one call)
+ * and on the host: EWAL_E_INVAL for a NULL ctx, for d_groups, d_resps, d_res
+ * NULL (or d_ents NULL with a non-zero count) while n > 0, for d_groups,
+ * d_snaps, d_resps, d_res, d_msgs not 16-byte aligned or d_ents not 8-byte
+ * aligned, and for n or G >= 2^31 - 1.  n == 0: EWAL_OK, counters 0.
+ * A compute call on the ctx's stream (ewal_ctx_set_stream) like the others;
+ * ewal_last_device_ms covers it; a repeated call of the same or a smaller
+ * shape allocates nothing. */
+int elead_step_batch_device(ewal_ctx *ctx, elead_group *d_groups, uint64_t G,
+                            const elead_snap *d_snaps /* G, nullable */,
+                            const ewal_entry *d_ents, uint64_t n_ents_total,
+                            const elead_resp *d_resps, uint64_t n,
+                            elead_result *d_res,
+                            struct emsg_out *d_msgs /* NULL: size query */, uint64_t msgs_cap,
+                            uint64_t *n_msgs, uint64_t *n_committed);
+/* For bindings / tests: the sizes of the four records. */
+uint32_t elead_group_size(void);
+uint32_t elead_snap_size(void);
+uint32_t elead_resp_size(void);
+uint32_t elead_result_size(void);
 
 /* ---- raft ingress: raftpb.Message.Unmarshal, raft/raftpb/raft.pb.go:407-617
  * (called per POST /raft in etcdserver/etcdhttp/http.go:119-146), batched
