@@ -1,4 +1,5 @@
-// aux_kernels.hip -- snapshot CRC batch verify and batched raft quorum commit.
+// aux_kernels.hip -- snapshot CRC batch verify, batched raft quorum commit and
+// the batched WAL write pipeline.
 //
 //   k_snap    snap.loadSnap (snap/snapshotter.go:76-111): snappb.Snapshot
 //             Unmarshal (snap/snappb/snap.pb.go:42-120), crc32.Update(0, tab,
@@ -9,8 +10,12 @@
 //   k_commit  raft.maybeCommit (raft/raft.go:248-258, q() :275-277) +
 //             raftLog.maybeCommit / term / at / isOutOfBounds
 //             (raft/log.go:115-154, 194-217), one lane per raft group.
+//   k_wr_*    (*WAL).SaveEntry / SaveState / Cut (wal/wal.go:219-279) over a
+//             batch of records: sizes, bodies, one stream pass for every
+//             chained CRC, frames (the banner further down).
 #include "ewal_device.h"
 #include "ewal_internal.h"
+#include "ewal_wire.h"
 
 __global__ __launch_bounds__(256) void k_snap(const uint8_t *__restrict__ buf, const uint32_t *__restrict__ pwave,
                        const uint32_t *__restrict__ v, const uint32_t *__restrict__ g_slice,
@@ -365,35 +370,53 @@ __global__ __launch_bounds__(64) void k_commit_rec(uint64_t G, const ecommit_gro
 }
 
 // ===========================================================================
-// Batched encoder.encode of entries (wal/wal.go:248-263 SaveEntry,
-// wal/encoder.go:25-37): frame_i = int64 LE len || walpb.Record{Type: 2, Crc:
-// c_i, Data: E_i}, E_i = raftpb.Entry.Marshal() (raft/raftpb/raft.pb.go:
-// 921-943), c_i = crc32.Update(c_{i-1}, Castagnoli, E_i).  The CRC chain
-// runs over the contiguous "data-only" stream E_0 || E_1 || ... (frame
-// headers are not in it), so ONE stream pass gives every c_i:
-// c_i = ~P(end of E_i) once the stream's first 4 bytes are XORed with
-// ~c_{-1} (a reflected CRC register started at r equals one started at 0 over
-// the message whose first 4 bytes are XORed with r).
+// Batched WAL writes, one pipeline for both entry points: SaveEntry over an
+// ewal_entry[] (ewal_encode_entries_device; wal/wal.go:248-263) and Save
+// (SaveState + SaveEntry, wal/wal.go:248-279) + Cut (wal/wal.go:219-238: a
+// crcType record carrying the running CRC, then the metadata record) over an
+// ewal_save_rec[] (ewal_save_device), as ONE chained call.  frame = int64 LE
+// len || walpb.Record{Type, Crc, Data} (wal/encoder.go:25-37); every header
+// byte comes from ewal_wire.h.  Every record contributes one contiguous chunk
+// to the "data-only" stream (Entry / HardState marshal, the Cut's metadata
+// bytes; a crcType record adds nothing: Data is nil; frame headers are not in
+// it), so ONE stream pass gives every chained CRC:
+//   crc after the chunk ending at x = ~(P'(x) ^ (x < 4 ? R0 >> 8x : 0)),
+// P' over the stream whose first min(4, E) bytes are XORed with R0 = ~prev
+// (a reflected register started at R0 over k < 4 bytes equals one started at
+// 0 over the XORed bytes, then XORed with R0 >> 8k).
+//
+// The kernels are templates over the record layout R and read it through
+// wr_view: for R = ewal_entry the kind is a constant, so the HardState and
+// Cut branches and pcrc fold away.
 // ===========================================================================
-__device__ __forceinline__ uint32_t sov64(uint64_t x) {
-  uint32_t n = 1;
-  while (x >= 0x80) { x >>= 7; ++n; }
-  return n;
+using ewal_wire::entry_head;
+using ewal_wire::entry_size;
+using ewal_wire::frame_head;
+using ewal_wire::frame_size;
+using ewal_wire::sov;
+using ewal_wire::state_marshal;
+
+struct WrRec {
+  int32_t kind, etype;
+  uint64_t a, b, c, data_off, data_len;
+  bool data_nil;
+};
+// Entry.Marshal always writes 22 v(len): a nil Data encodes as an empty one
+__device__ __forceinline__ WrRec wr_view(const ewal_entry &e) {
+  return WrRec{EWAL_SAVE_ENTRY, e.type, e.term, e.index, 0, e.data_off, e.data_len, false};
 }
-__device__ __forceinline__ uint32_t put_varint_dev(uint8_t *o, uint64_t v) {
-  uint32_t n = 0;
-  while (v >= 0x80) { o[n++] = (uint8_t)(v | 0x80); v >>= 7; }
-  o[n++] = (uint8_t)v;
-  return n;
+__device__ __forceinline__ WrRec wr_view(const ewal_save_rec &r) {
+  return WrRec{r.kind, r.etype, r.a, r.b, r.c, r.data_off, r.data_len, r.data_nil != 0};
 }
-// Entry header 08 v(type) 10 v(term) 18 v(index) 22 v(len) into h (<= 44 B)
-__device__ __forceinline__ uint32_t entry_head(uint8_t *h, const ewal_entry &e) {
-  uint32_t o = 0;
-  h[o++] = 0x08; o += put_varint_dev(h + o, (uint64_t)(int64_t)e.type);
-  h[o++] = 0x10; o += put_varint_dev(h + o, e.term);
-  h[o++] = 0x18; o += put_varint_dev(h + o, e.index);
-  h[o++] = 0x22; o += put_varint_dev(h + o, e.data_len);
-  return o;
+
+// the first hl <= N bytes of h -> dst, one byte a lane.  h lives in the lane's scratch (the varints index it at
+// run time), so the lane reads its byte there: a select over N registers instead keeps N lane masks in SGPRs
+// across the record loop and costs the kernel a wave of occupancy.
+template <int N>
+__device__ __forceinline__ void wave_put(uint8_t *__restrict__ dst, const uint8_t (&h)[N], uint32_t hl) {
+  static_assert(N <= 64, "one byte a lane");
+  const int lane = threadIdx.x & 63;
+  if ((uint32_t)lane < hl) dst[lane] = h[lane];
 }
 
 // Wave-cooperative copy of n bytes src -> dst (any alignment): byte stores for
@@ -427,126 +450,22 @@ __device__ __forceinline__ void wave_copy(uint8_t *__restrict__ dst, const uint8
   if ((uint64_t)lane < n - t0) dst[t0 + lane] = src[t0 + lane];
 }
 
-// esz[i] = |E_i|
-__global__ void k_enc_sizes(const ewal_entry *__restrict__ ents, uint64_t n, uint64_t data_len,
-                            uint64_t *__restrict__ esz, uint32_t *__restrict__ errflag) {
+// esz[i] = chunk size of record i (0: no chunk -- an empty HardState writes
+// nothing, raft.IsEmptyHardState, wal/wal.go:266-268); errflag: a payload
+// outside d_data (entries and non-nil Cut metadata only) or an unknown kind
+template <typename R>
+__global__ void k_wr_sizes(const R *__restrict__ recs, uint64_t n, uint64_t data_len, uint64_t *__restrict__ esz,
+                           uint32_t *__restrict__ errflag) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const ewal_entry e = ents[i];
-  if (e.data_len > data_len || e.data_off > data_len - e.data_len) atomicOr(errflag, 1u);   // outside d_data
-  esz[i] = 4 + sov64((uint64_t)(int64_t)e.type) + sov64(e.term) + sov64(e.index) + sov64(e.data_len) + e.data_len;
-}
-
-// E_i at xoff[i] of the data-only stream; one wave per entry (grid-stride)
-__global__ __launch_bounds__(256) void k_enc_body(const uint8_t *__restrict__ data, uint64_t data_len,
-                                                  const ewal_entry *__restrict__ ents, uint64_t n,
-                                                  const uint64_t *__restrict__ xoff, uint8_t *__restrict__ es) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x >> 6);
-  for (uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < n; i += nw) {
-    const ewal_entry e = ents[i];
-    uint8_t h[48];
-    const uint32_t hl = entry_head(h, e);
-    uint8_t *o = es + xoff[i];
-    if ((uint32_t)lane < hl) {
-      uint8_t b = 0;
-#pragma unroll
-      for (int k = 0; k < 48; ++k) b = (k == lane) ? h[k] : b;
-      o[lane] = b;
-    }
-    if (e.data_len) wave_copy(o + hl, data + e.data_off, e.data_len, data, data_len);
-  }
-}
-
-// XOR the data-only stream's first 4 bytes with r (and back)
-__global__ void k_enc_xor4(uint8_t *es, uint32_t r) {
-  if (threadIdx.x < 4) es[threadIdx.x] ^= (uint8_t)(r >> (8 * threadIdx.x));
-}
-
-// c_i = ~P(end of E_i); frame size fsz[i] = 8 + |Record|
-__global__ __launch_bounds__(256) void k_enc_crc(const uint8_t *__restrict__ es, const uint64_t *__restrict__ xoff,
-                                                 const uint64_t *__restrict__ esz, uint64_t n,
-                                                 const uint32_t *__restrict__ pwave, const uint32_t *__restrict__ v,
-                                                 const uint32_t *__restrict__ g_slice,
-                                                 const uint32_t *__restrict__ g_shift, uint32_t *__restrict__ crc,
-                                                 uint64_t *__restrict__ fsz) {
-  __shared__ uint32_t s_t4[1024];
-  __shared__ uint32_t s_svp[1024];
-  stage_lds<256>(s_t4, 1024, [&](int i) { return g_slice[i]; });
-  stage_lds<256>(s_svp, 1024, [&](int i) { return g_shift[EW_VLOG * 1024 + i]; });
-  __syncthreads();
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t L = esz[i];
-  const uint32_t c = ~prefix_at(xoff[i] + L, pwave, v, es, s_t4, s_svp);
-  crc[i] = c;
-  fsz[i] = 8 + 1 + 1 + 1 + sov64(c) + 1 + sov64(L) + L;   // 08 02 10 v(c) 1a v(L) E
-}
-
-// frame_i at foff[i]: int64 len, 08 02 10 v(c) 1a v(|E_i|), E_i; one wave per entry
-__global__ __launch_bounds__(256) void k_enc_frame(const uint8_t *__restrict__ es, uint64_t es_len,
-                                                   const uint64_t *__restrict__ xoff,
-                                                   const uint64_t *__restrict__ esz, const uint32_t *__restrict__ crc,
-                                                   const uint64_t *__restrict__ foff, uint64_t n,
-                                                   uint8_t *__restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x >> 6);
-  for (uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < n; i += nw) {
-    const uint64_t L = esz[i];
-    const uint32_t c = crc[i];
-    uint8_t h[32];
-    uint32_t o = 8;
-    h[o++] = 0x08; h[o++] = 0x02;
-    h[o++] = 0x10; o += put_varint_dev(h + o, c);
-    h[o++] = 0x1a; o += put_varint_dev(h + o, L);
-    const uint64_t rec = (uint64_t)(o - 8) + L;             // the int64 length prefix
-#pragma unroll
-    for (int k = 0; k < 8; ++k) h[k] = (uint8_t)(rec >> (8 * k));
-    uint8_t *dst = out + foff[i];
-    if ((uint32_t)lane < o) {
-      uint8_t b = 0;
-#pragma unroll
-      for (int k = 0; k < 32; ++k) b = (k == lane) ? h[k] : b;
-      dst[lane] = b;
-    }
-    wave_copy(dst + o, es + xoff[i], L, es, es_len);
-  }
-}
-
-// ===========================================================================
-// Batched WAL writes: Save (SaveState + SaveEntry, wal/wal.go:248-279) and Cut
-// (wal/wal.go:219-238: a crcType record carrying the running CRC, then the
-// metadata record) as ONE chained call.  Every save record contributes one
-// contiguous chunk to the data-only stream (Entry / HardState marshal, the
-// Cut's metadata bytes; a crcType record adds nothing: Data is nil), so ONE
-// stream pass gives every chained CRC as in k_enc_*:
-//   crc after the chunk ending at x = ~(P'(x) ^ (x < 4 ? R0 >> 8x : 0)),
-// P' over the stream whose first min(4, E) bytes are XORed with R0 = ~prev
-// (a reflected register started at R0 over k < 4 bytes equals one started at
-// 0 over the XORed bytes, then XORed with R0 >> 8k).
-// ===========================================================================
-__device__ __forceinline__ uint32_t hardstate_head(uint8_t *h, uint64_t term, uint64_t vote, uint64_t commit) {
-  uint32_t o = 0;
-  h[o++] = 0x08; o += put_varint_dev(h + o, term);
-  h[o++] = 0x10; o += put_varint_dev(h + o, vote);
-  h[o++] = 0x18; o += put_varint_dev(h + o, commit);
-  return o;
-}
-
-// chunk size of save record i (0: no chunk -- an empty HardState writes
-// nothing, raft.IsEmptyHardState, wal/wal.go:266-268)
-__global__ void k_save_sizes(const ewal_save_rec *__restrict__ recs, uint64_t n, uint64_t data_len,
-                             uint64_t *__restrict__ esz, uint32_t *__restrict__ errflag) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const ewal_save_rec r = recs[i];
+  const WrRec r = wr_view(recs[i]);
   uint64_t z = 0;
-  const bool hasd = (r.kind == EWAL_SAVE_ENTRY || r.kind == EWAL_SAVE_CUT) && !(r.kind == EWAL_SAVE_CUT && r.data_nil);
+  const bool hasd = r.kind == EWAL_SAVE_ENTRY || (r.kind == EWAL_SAVE_CUT && !r.data_nil);
   if (hasd && (r.data_len > data_len || r.data_off > data_len - r.data_len)) atomicOr(errflag, 1u);
   if (r.kind == EWAL_SAVE_ENTRY) {
-    z = 4 + sov64((uint64_t)(int64_t)r.etype) + sov64(r.a) + sov64(r.b) + sov64(r.data_len) + r.data_len;
+    z = entry_size(r.etype, r.a, r.b, r.data_len);
   } else if (r.kind == EWAL_SAVE_STATE) {
-    if (r.a | r.b | r.c) z = 3 + sov64(r.a) + sov64(r.b) + sov64(r.c);
+    if (r.a | r.b | r.c) z = 3 + sov(r.a) + sov(r.b) + sov(r.c);
   } else if (r.kind == EWAL_SAVE_CUT) {
     z = r.data_nil ? 0 : r.data_len;
   } else {
@@ -555,59 +474,52 @@ __global__ void k_save_sizes(const ewal_save_rec *__restrict__ recs, uint64_t n,
   esz[i] = z;
 }
 
-// chunk i at xoff[i]; one wave per record (grid-stride)
-__global__ __launch_bounds__(256) void k_save_body(const uint8_t *__restrict__ data, uint64_t data_len,
-                                                   const ewal_save_rec *__restrict__ recs, uint64_t n,
-                                                   const uint64_t *__restrict__ xoff, uint8_t *__restrict__ es) {
-  const int lane = threadIdx.x & 63;
+// chunk i at xoff[i] of the data-only stream; one wave per record (grid-stride)
+template <typename R>
+__global__ __launch_bounds__(256) void k_wr_body(const uint8_t *__restrict__ data, uint64_t data_len,
+                                                 const R *__restrict__ recs, uint64_t n,
+                                                 const uint64_t *__restrict__ xoff, uint8_t *__restrict__ es) {
   const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x >> 6);
   for (uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < n; i += nw) {
-    const ewal_save_rec r = recs[i];
+    const WrRec r = wr_view(recs[i]);
     uint8_t h[48];
     uint32_t hl = 0;
     uint64_t dl = 0;
     if (r.kind == EWAL_SAVE_ENTRY) {
-      ewal_entry e;
-      e.type = r.etype; e.term = r.a; e.index = r.b; e.data_len = r.data_len;
-      hl = entry_head(h, e);
+      hl = (uint32_t)(entry_head(h, r.etype, r.a, r.b, r.data_len) - h);
       dl = r.data_len;
     } else if (r.kind == EWAL_SAVE_STATE) {
-      if (r.a | r.b | r.c) hl = hardstate_head(h, r.a, r.b, r.c);
+      if (r.a | r.b | r.c) hl = (uint32_t)state_marshal(h, r.a, r.b, r.c);
     } else if (r.kind == EWAL_SAVE_CUT && !r.data_nil) {
       dl = r.data_len;
     }
     uint8_t *o = es + xoff[i];
-    if ((uint32_t)lane < hl) {
-      uint8_t b = 0;
-#pragma unroll
-      for (int k = 0; k < 48; ++k) b = (k == lane) ? h[k] : b;
-      o[lane] = b;
-    }
+    wave_put(o, h, hl);
     if (dl) wave_copy(o + hl, data + r.data_off, dl, data, data_len);
   }
 }
 
 // XOR the stream's first min(4, E) bytes with r (and back)
-__global__ void k_save_xor4(uint8_t *es, uint64_t E, uint32_t r) {
+__global__ void k_wr_xor4(uint8_t *es, uint64_t E, uint32_t r) {
   if (threadIdx.x < 4 && threadIdx.x < E) es[threadIdx.x] ^= (uint8_t)(r >> (8 * threadIdx.x));
 }
 
-__device__ __forceinline__ uint32_t save_crc_at(uint64_t x, uint32_t R0, uint64_t E, const uint32_t *pwave,
-                                                const uint32_t *v, const uint8_t *es, const uint32_t *t4,
-                                                const uint32_t *svp) {
+__device__ __forceinline__ uint32_t wr_crc_at(uint64_t x, uint32_t R0, uint64_t E, const uint32_t *pwave,
+                                              const uint32_t *v, const uint8_t *es, const uint32_t *t4,
+                                              const uint32_t *svp) {
   const uint32_t p = (E && x) ? prefix_at(x, pwave, v, es, t4, svp) : 0u;
   return ~(p ^ (x < 4 ? (R0 >> (8 * x)) : 0u));
 }
 
 // crc[i] = the running CRC after record i's chunk (its Record.Crc), pcrc[i]
 // = before it (a Cut's crcType record); fsz[i] = bytes of record i's frames
-__global__ __launch_bounds__(256) void k_save_crc(const uint8_t *__restrict__ es, uint64_t E,
-                                                  const ewal_save_rec *__restrict__ recs,
-                                                  const uint64_t *__restrict__ xoff, const uint64_t *__restrict__ esz,
-                                                  uint64_t n, uint32_t R0, const uint32_t *__restrict__ pwave,
-                                                  const uint32_t *__restrict__ v, const uint32_t *__restrict__ g_slice,
-                                                  const uint32_t *__restrict__ g_shift, uint32_t *__restrict__ crc,
-                                                  uint32_t *__restrict__ pcrc, uint64_t *__restrict__ fsz) {
+template <typename R>
+__global__ __launch_bounds__(256) void k_wr_crc(const uint8_t *__restrict__ es, uint64_t E, const R *__restrict__ recs,
+                                                const uint64_t *__restrict__ xoff, const uint64_t *__restrict__ esz,
+                                                uint64_t n, uint32_t R0, const uint32_t *__restrict__ pwave,
+                                                const uint32_t *__restrict__ v, const uint32_t *__restrict__ g_slice,
+                                                const uint32_t *__restrict__ g_shift, uint32_t *__restrict__ crc,
+                                                uint32_t *__restrict__ pcrc, uint64_t *__restrict__ fsz) {
   __shared__ uint32_t s_t4[1024];
   __shared__ uint32_t s_svp[1024];
   stage_lds<256>(s_t4, 1024, [&](int i) { return g_slice[i]; });
@@ -615,61 +527,51 @@ __global__ __launch_bounds__(256) void k_save_crc(const uint8_t *__restrict__ es
   __syncthreads();
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const ewal_save_rec r = recs[i];
+  const WrRec r = wr_view(recs[i]);
   const uint64_t L = esz[i];
-  const uint32_t c = save_crc_at(xoff[i] + L, R0, E, pwave, v, es, s_t4, s_svp);
+  const uint32_t c = wr_crc_at(xoff[i] + L, R0, E, pwave, v, es, s_t4, s_svp);
   crc[i] = c;
   uint64_t f = 0;
   if (r.kind == EWAL_SAVE_ENTRY || (r.kind == EWAL_SAVE_STATE && L)) {
-    f = 8 + 1 + 1 + 1 + sov64(c) + 1 + sov64(L) + L;              // 08 t 10 v(c) 1a v(L) chunk
+    f = frame_size(r.kind == EWAL_SAVE_ENTRY ? 2 : 3, c, L, false);   // entryType, stateType
   } else if (r.kind == EWAL_SAVE_CUT) {
-    const uint32_t c0 = save_crc_at(xoff[i], R0, E, pwave, v, es, s_t4, s_svp);
+    const uint32_t c0 = wr_crc_at(xoff[i], R0, E, pwave, v, es, s_t4, s_svp);
     pcrc[i] = c0;
-    f = 8 + 1 + 1 + 1 + sov64(c0);                                 // crcType: 08 04 10 v(c0), Data nil
-    f += 8 + 1 + 1 + 1 + sov64(c) + (r.data_nil ? 0 : 1 + sov64(L) + L);   // metadataType
+    f = frame_size(4, c0, 0, true) + frame_size(1, c, L, r.data_nil);   // crcType (Data nil), metadataType
   }
   fsz[i] = f;
 }
 
-// one frame (int64 len || 08 t 10 v(c) [1a v(L) chunk]) at dst; one wave
-__device__ __forceinline__ void save_frame(uint8_t *dst, int32_t t, uint32_t c, bool hasd, const uint8_t *chunk,
-                                           uint64_t L, const uint8_t *es, uint64_t es_len) {
-  const int lane = threadIdx.x & 63;
+// one frame (frame_head, then the L chunk bytes unless nil) at dst; one wave
+__device__ __forceinline__ void wr_frame(uint8_t *dst, int32_t t, uint32_t c, bool nil, const uint8_t *chunk, uint64_t L,
+                                         const uint8_t *es, uint64_t es_len) {
   uint8_t h[32];
-  uint32_t o = 8;
-  h[o++] = 0x08; h[o++] = (uint8_t)t;
-  h[o++] = 0x10; o += put_varint_dev(h + o, c);
-  if (hasd) { h[o++] = 0x1a; o += put_varint_dev(h + o, L); }
-  const uint64_t rec = (uint64_t)(o - 8) + (hasd ? L : 0);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) h[k] = (uint8_t)(rec >> (8 * k));
-  if ((uint32_t)lane < o) {
-    uint8_t b = 0;
-#pragma unroll
-    for (int k = 0; k < 32; ++k) b = (k == lane) ? h[k] : b;
-    dst[lane] = b;
-  }
-  if (hasd && L) wave_copy(dst + o, chunk, L, es, es_len);
+  const uint32_t hl = frame_head(h, t, c, L, nil);
+  wave_put(dst, h, hl);
+  // no branch around the copy (0 bytes copy nothing): a chunk address loaded for a copy that is then skipped
+  // stays in flight, and the record loop's next trip would start by waiting for it and for this trip's stores
+  wave_copy(dst + hl, chunk, nil ? 0 : L, es, es_len);
 }
 
-__global__ __launch_bounds__(256) void k_save_frame(const uint8_t *__restrict__ es, uint64_t es_len,
-                                                    const ewal_save_rec *__restrict__ recs,
-                                                    const uint64_t *__restrict__ xoff, const uint64_t *__restrict__ esz,
-                                                    const uint32_t *__restrict__ crc, const uint32_t *__restrict__ pcrc,
-                                                    const uint64_t *__restrict__ foff, uint64_t n,
-                                                    uint8_t *__restrict__ out) {
+// record i's frames at foff[i]; one wave per record (grid-stride)
+template <typename R>
+__global__ __launch_bounds__(256) void k_wr_frame(const uint8_t *__restrict__ es, uint64_t es_len,
+                                                  const R *__restrict__ recs, const uint64_t *__restrict__ xoff,
+                                                  const uint64_t *__restrict__ esz, const uint32_t *__restrict__ crc,
+                                                  const uint32_t *__restrict__ pcrc, const uint64_t *__restrict__ foff,
+                                                  uint64_t n, uint8_t *__restrict__ out) {
   const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x >> 6);
   for (uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < n; i += nw) {
-    const ewal_save_rec r = recs[i];
+    const WrRec r = wr_view(recs[i]);
     const uint64_t L = esz[i];
     uint8_t *dst = out + foff[i];
-    if (r.kind == EWAL_SAVE_ENTRY || (r.kind == EWAL_SAVE_STATE && L)) {
-      save_frame(dst, r.kind == EWAL_SAVE_ENTRY ? 2 : 3, crc[i], true, es + xoff[i], L, es, es_len);
+    // | and &, not || and &&: L is read on every path, so its load is never left in flight either
+    if ((r.kind == EWAL_SAVE_ENTRY) | ((r.kind == EWAL_SAVE_STATE) & (L != 0))) {
+      wr_frame(dst, r.kind == EWAL_SAVE_ENTRY ? 2 : 3, crc[i], false, es + xoff[i], L, es, es_len);
     } else if (r.kind == EWAL_SAVE_CUT) {
       const uint32_t c0 = pcrc[i];
-      save_frame(dst, 4, c0, false, nullptr, 0, es, es_len);
-      dst += 8 + 1 + 1 + 1 + sov64(c0);
-      save_frame(dst, 1, crc[i], !r.data_nil, es + xoff[i], L, es, es_len);
+      wr_frame(dst, 4, c0, true, es, 0, es, es_len);
+      wr_frame(dst + frame_size(4, c0, 0, true), 1, crc[i], r.data_nil, es + xoff[i], L, es, es_len);
     }
   }
 }

@@ -313,6 +313,15 @@ static int select_flagged(ewal_ctx *c, const uint8_t *flags, uint32_t n, uint32_
   return 0;
 }
 
+// hipcub DeviceScan::ExclusiveSum(in) -> out over n < 2^31 items
+static int exclusive_sum(ewal_ctx *c, const uint64_t *in, uint64_t *out, uint64_t n) {
+  size_t bytes = 0;
+  EW_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, c->stream));
+  EW_CHECK(c->tmp.ensure(bytes));
+  EW_CHECK(hipcub::DeviceScan::ExclusiveSum(c->tmp.p, bytes, in, out, (int)n, c->stream));
+  return 0;
+}
+
 // The general framing path's per-candidate arrays (lengths, links, link
 // exceptions): allocated only when that path runs, so the regular path's
 // first call does not pay for them.
@@ -2200,6 +2209,69 @@ static int materialise_records(ewal_ctx *c) {
   return 0;
 }
 
+// The batched write path of ewal_encode_entries_device (R = ewal_entry) and
+// ewal_save_device (R = ewal_save_rec), aux_kernels.hip k_wr_*: n >= 1 records
+// -> their frames in d_out.  The host decides three times: after the chunk
+// sizes (errflag, E = bytes of the data-only stream), after the frame sizes
+// (the total against cap, last_crc, the offsets) and at the final sync.
+template <typename R>
+static int write_chain(ewal_ctx *c, const void *d_data, uint64_t data_len_total, const R *d_recs, uint64_t n,
+                       uint32_t prev_crc, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *last_crc,
+                       uint64_t *h_rec_off) {
+  EW_CHECK(hipSetDevice(c->device));
+  DevTables *tb;
+  int rc = get_tables(c, 0x82F63B78u, &tb);
+  if (rc) return rc;
+  EW_CHECK(c->small.ensure(sizeof(Small)));
+  Small *ds = c->small.as<Small>();
+  EW_CHECK(hipMemsetAsync(&ds->errflag, 0, 4, c->stream));
+  // per-record scratch: esz, xoff, fsz, foff (u64) + crc, pcrc (u32; pcrc: Cuts only)
+  EW_CHECK(c->encw.ensure((size_t)n * 40 + 64));
+  uint64_t *esz = c->encw.as<uint64_t>(), *xoff = esz + n, *fsz = xoff + n, *foff = fsz + n;
+  uint32_t *crc = (uint32_t *)(foff + n), *pcrc = crc + n;
+  hipLaunchKernelGGL(k_wr_sizes<R>, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, d_recs, n, data_len_total, esz,
+                     &ds->errflag);
+  if ((rc = exclusive_sum(c, esz, xoff, n))) return rc;
+  uint64_t tail[2];
+  uint32_t bad = 0;
+  EW_CHECK(hipMemcpyAsync(&tail[0], xoff + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipMemcpyAsync(&tail[1], esz + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipMemcpyAsync(&bad, &ds->errflag, 4, hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  if (bad) return EWAL_E_INVAL;
+  const uint64_t E = tail[0] + tail[1];                 // bytes of the data-only stream
+  EW_CHECK(c->encs.ensure(E + 64));
+  uint8_t *es = c->encs.as<uint8_t>();
+  const unsigned wgrid = (unsigned)std::min<uint64_t>(grid_for(n, 4), (uint64_t)c->num_cu * 8);
+  const uint32_t R0 = ~prev_crc;
+  hipLaunchKernelGGL(k_wr_body<R>, dim3(wgrid), dim3(256), 0, c->stream, (const uint8_t *)d_data, data_len_total,
+                     d_recs, n, xoff, es);
+  if (E) {   // E == 0 (only empty HardStates and nil Cuts): no stream pass, every CRC is prev_crc
+    hipLaunchKernelGGL(k_wr_xor4, dim3(1), dim3(64), 0, c->stream, es, E, R0);
+    rc = run_stream(c, tb, es, E, 0, 0);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(k_wr_crc<R>, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, es, E, d_recs, xoff, esz, n, R0,
+                     c->pwave.as<uint32_t>(), c->v.as<uint32_t>(), tb->slice, tb->shift, crc, pcrc, fsz);
+  if (E) hipLaunchKernelGGL(k_wr_xor4, dim3(1), dim3(64), 0, c->stream, es, E, R0);   // the bytes back
+  if ((rc = exclusive_sum(c, fsz, foff, n))) return rc;
+  uint32_t lc = 0;
+  EW_CHECK(hipMemcpyAsync(&tail[0], foff + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipMemcpyAsync(&tail[1], fsz + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipMemcpyAsync(&lc, crc + n - 1, 4, hipMemcpyDeviceToHost, c->stream));
+  if (h_rec_off) EW_CHECK(hipMemcpyAsync(h_rec_off, foff, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  const uint64_t total = tail[0] + tail[1];
+  if (total > cap) return EWAL_E_NOMEM;
+  hipLaunchKernelGGL(k_wr_frame<R>, dim3(wgrid), dim3(256), 0, c->stream, es, E, d_recs, xoff, esz, crc, pcrc, foff, n,
+                     (uint8_t *)d_out);
+  EW_CHECK(hipGetLastError());
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  *out_len = total;
+  *last_crc = lc;
+  return EWAL_OK;
+}
+
 extern "C" {
 
 int ewal_device_count(void) {
@@ -2719,59 +2791,7 @@ int ewal_encode_entries_device(ewal_ctx *c, const void *d_data, uint64_t data_le
   *last_crc = prev_crc;
   if (n == 0) return EWAL_OK;
   if (n >= 0x7fffffffull) return EWAL_E_INVAL;
-  EW_CHECK(hipSetDevice(c->device));
-  DevTables *tb;
-  int rc = get_tables(c, 0x82F63B78u, &tb);
-  if (rc) return rc;
-  EW_CHECK(c->small.ensure(sizeof(Small)));
-  Small *ds = c->small.as<Small>();
-  EW_CHECK(hipMemsetAsync(&ds->errflag, 0, 4, c->stream));
-  // per-entry scratch: esz, xoff, fsz, foff (u64) + crc (u32)
-  EW_CHECK(c->encw.ensure((size_t)n * 36 + 64));
-  uint64_t *esz = c->encw.as<uint64_t>(), *xoff = esz + n, *fsz = xoff + n, *foff = fsz + n;
-  uint32_t *crc = (uint32_t *)(foff + n);
-  hipLaunchKernelGGL(k_enc_sizes, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, d_ents, n, data_len_total, esz,
-                     &ds->errflag);
-  size_t tbytes = 0;
-  EW_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tbytes, esz, xoff, (int)n, c->stream));
-  EW_CHECK(c->tmp.ensure(tbytes));
-  EW_CHECK(hipcub::DeviceScan::ExclusiveSum(c->tmp.p, tbytes, esz, xoff, (int)n, c->stream));
-  uint64_t tail[2];
-  uint32_t bad = 0;
-  EW_CHECK(hipMemcpyAsync(&tail[0], xoff + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
-  EW_CHECK(hipMemcpyAsync(&tail[1], esz + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
-  EW_CHECK(hipMemcpyAsync(&bad, &ds->errflag, 4, hipMemcpyDeviceToHost, c->stream));
-  EW_CHECK(hipStreamSynchronize(c->stream));
-  if (bad) return EWAL_E_INVAL;
-  const uint64_t E = tail[0] + tail[1];                 // bytes of the data-only stream
-  EW_CHECK(c->encs.ensure(E + 64));
-  uint8_t *es = c->encs.as<uint8_t>();
-  const unsigned wgrid = (unsigned)std::min<uint64_t>(grid_for(n, 4), (uint64_t)c->num_cu * 8);
-  hipLaunchKernelGGL(k_enc_body, dim3(wgrid), dim3(256), 0, c->stream, (const uint8_t *)d_data, data_len_total,
-                     d_ents, n, xoff, es);
-  hipLaunchKernelGGL(k_enc_xor4, dim3(1), dim3(64), 0, c->stream, es, ~prev_crc);
-  rc = run_stream(c, tb, es, E, 0, 0);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_enc_crc, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, es, xoff, esz, n,
-                     c->pwave.as<uint32_t>(), c->v.as<uint32_t>(), tb->slice, tb->shift, crc, fsz);
-  hipLaunchKernelGGL(k_enc_xor4, dim3(1), dim3(64), 0, c->stream, es, ~prev_crc);   // the bytes back
-  EW_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tbytes, fsz, foff, (int)n, c->stream));
-  EW_CHECK(c->tmp.ensure(tbytes));
-  EW_CHECK(hipcub::DeviceScan::ExclusiveSum(c->tmp.p, tbytes, fsz, foff, (int)n, c->stream));
-  uint32_t lc = 0;
-  EW_CHECK(hipMemcpyAsync(&tail[0], foff + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
-  EW_CHECK(hipMemcpyAsync(&tail[1], fsz + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
-  EW_CHECK(hipMemcpyAsync(&lc, crc + n - 1, 4, hipMemcpyDeviceToHost, c->stream));
-  EW_CHECK(hipStreamSynchronize(c->stream));
-  const uint64_t total = tail[0] + tail[1];
-  if (total > cap) return EWAL_E_NOMEM;
-  hipLaunchKernelGGL(k_enc_frame, dim3(wgrid), dim3(256), 0, c->stream, es, E, xoff, esz, crc, foff, n,
-                     (uint8_t *)d_out);
-  EW_CHECK(hipGetLastError());
-  EW_CHECK(hipStreamSynchronize(c->stream));
-  *out_len = total;
-  *last_crc = lc;
-  return EWAL_OK;
+  return write_chain(c, d_data, data_len_total, d_ents, n, prev_crc, d_out, cap, out_len, last_crc, nullptr);
 }
 
 int ewal_save_device(ewal_ctx *c, const void *d_data, uint64_t data_len_total, const ewal_save_rec *d_recs, uint64_t n,
@@ -2782,63 +2802,7 @@ int ewal_save_device(ewal_ctx *c, const void *d_data, uint64_t data_len_total, c
   *last_crc = prev_crc;
   if (n == 0) return EWAL_OK;
   if (n >= 0x7fffffffull) return EWAL_E_INVAL;
-  EW_CHECK(hipSetDevice(c->device));
-  DevTables *tb;
-  int rc = get_tables(c, 0x82F63B78u, &tb);
-  if (rc) return rc;
-  EW_CHECK(c->small.ensure(sizeof(Small)));
-  Small *ds = c->small.as<Small>();
-  EW_CHECK(hipMemsetAsync(&ds->errflag, 0, 4, c->stream));
-  // per-record scratch: esz, xoff, fsz, foff (u64) + crc, pcrc (u32)
-  EW_CHECK(c->encw.ensure((size_t)n * 40 + 64));
-  uint64_t *esz = c->encw.as<uint64_t>(), *xoff = esz + n, *fsz = xoff + n, *foff = fsz + n;
-  uint32_t *crc = (uint32_t *)(foff + n), *pcrc = crc + n;
-  hipLaunchKernelGGL(k_save_sizes, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, d_recs, n, data_len_total, esz,
-                     &ds->errflag);
-  size_t tbytes = 0;
-  EW_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tbytes, esz, xoff, (int)n, c->stream));
-  EW_CHECK(c->tmp.ensure(tbytes));
-  EW_CHECK(hipcub::DeviceScan::ExclusiveSum(c->tmp.p, tbytes, esz, xoff, (int)n, c->stream));
-  uint64_t tail[2];
-  uint32_t bad = 0;
-  EW_CHECK(hipMemcpyAsync(&tail[0], xoff + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
-  EW_CHECK(hipMemcpyAsync(&tail[1], esz + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
-  EW_CHECK(hipMemcpyAsync(&bad, &ds->errflag, 4, hipMemcpyDeviceToHost, c->stream));
-  EW_CHECK(hipStreamSynchronize(c->stream));
-  if (bad) return EWAL_E_INVAL;
-  const uint64_t E = tail[0] + tail[1];                 // bytes of the data-only stream
-  EW_CHECK(c->encs.ensure(E + 64));
-  uint8_t *es = c->encs.as<uint8_t>();
-  const unsigned wgrid = (unsigned)std::min<uint64_t>(grid_for(n, 4), (uint64_t)c->num_cu * 8);
-  const uint32_t R0 = ~prev_crc;
-  hipLaunchKernelGGL(k_save_body, dim3(wgrid), dim3(256), 0, c->stream, (const uint8_t *)d_data, data_len_total,
-                     d_recs, n, xoff, es);
-  if (E) {
-    hipLaunchKernelGGL(k_save_xor4, dim3(1), dim3(64), 0, c->stream, es, E, R0);
-    rc = run_stream(c, tb, es, E, 0, 0);
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(k_save_crc, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, es, E, d_recs, xoff, esz, n, R0,
-                     c->pwave.as<uint32_t>(), c->v.as<uint32_t>(), tb->slice, tb->shift, crc, pcrc, fsz);
-  if (E) hipLaunchKernelGGL(k_save_xor4, dim3(1), dim3(64), 0, c->stream, es, E, R0);   // the bytes back
-  EW_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tbytes, fsz, foff, (int)n, c->stream));
-  EW_CHECK(c->tmp.ensure(tbytes));
-  EW_CHECK(hipcub::DeviceScan::ExclusiveSum(c->tmp.p, tbytes, fsz, foff, (int)n, c->stream));
-  uint32_t lc = 0;
-  EW_CHECK(hipMemcpyAsync(&tail[0], foff + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
-  EW_CHECK(hipMemcpyAsync(&tail[1], fsz + n - 1, 8, hipMemcpyDeviceToHost, c->stream));
-  EW_CHECK(hipMemcpyAsync(&lc, crc + n - 1, 4, hipMemcpyDeviceToHost, c->stream));
-  if (h_rec_off) EW_CHECK(hipMemcpyAsync(h_rec_off, foff, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  EW_CHECK(hipStreamSynchronize(c->stream));
-  const uint64_t total = tail[0] + tail[1];
-  if (total > cap) return EWAL_E_NOMEM;
-  hipLaunchKernelGGL(k_save_frame, dim3(wgrid), dim3(256), 0, c->stream, es, E, d_recs, xoff, esz, crc, pcrc, foff, n,
-                     (uint8_t *)d_out);
-  EW_CHECK(hipGetLastError());
-  EW_CHECK(hipStreamSynchronize(c->stream));
-  *out_len = total;
-  *last_crc = lc;
-  return EWAL_OK;
+  return write_chain(c, d_data, data_len_total, d_recs, n, prev_crc, d_out, cap, out_len, last_crc, h_rec_off);
 }
 
 int ewal_crc32_update_device(ewal_ctx *c, uint32_t crc, uint32_t poly, const void *d_buf, uint64_t n, uint32_t *out) {
@@ -3191,7 +3155,7 @@ int emsg_decode_batch_device(ewal_ctx *c, const void *d_buf, uint64_t buf_len, c
                      c->mlen.as<uint64_t>(), n, cnt, (const unsigned long long *)nullptr, scnt,
                      (const unsigned long long *)nullptr, (emsg_message *)nullptr, (ewal_entry *)nullptr,
                      (emsg_segment *)nullptr);
-  size_t bytes = 0;
+  size_t bytes = 0;   // one size query and one workspace for both scans (same type and count)
   EW_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt, first, (int)n, c->stream));
   EW_CHECK(c->tmp.ensure(bytes));
   EW_CHECK(hipcub::DeviceScan::ExclusiveSum(c->tmp.p, bytes, cnt, first, (int)n, c->stream));

@@ -692,7 +692,7 @@ uint64_t emsg_encode_size(const emsg_out *h_msgs, uint64_t n, const ewal_entry *
     if (__builtin_add_overflow(z, s, &z)) return ~0ull;
     for (uint64_t k = 0; k < m.n_ents; ++k) {
       const ewal_entry &en = h_ents[m.ents_first + k];
-      uint64_t l = 4 + sov((uint64_t)(int64_t)en.type) + sov(en.term) + sov(en.index) + sov(en.data_len);
+      uint64_t l = entry_size(en.type, en.term, en.index, en.data_len) - en.data_len;   // E's four fields
       if (__builtin_add_overflow(l, en.data_len, &l) || __builtin_add_overflow(z, l, &z) ||
           __builtin_add_overflow(z, (uint64_t)(1 + sov(l)), &z))
         return ~0ull;

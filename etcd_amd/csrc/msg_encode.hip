@@ -38,6 +38,7 @@
 // million heartbeats ~340 messages per tile, 5 or 6 per lane.
 #include "ewal_device.h"
 #include "ewal_internal.h"
+#include "ewal_wire.h"
 
 #define EME_RUN 128u                           // contiguous output bytes per lane and tile
 #define EME_TILE (64u * EME_RUN)               // bytes of d_out per wave
@@ -70,12 +71,8 @@ struct EmeArgs {
   uint64_t total;
 };
 
-// sov64 without its loop: the body kernel takes varint widths by the dozen
-__device__ __forceinline__ uint32_t eme_sov(uint64_t x) { return (70u - (uint32_t)__clzll((long long)(x | 1))) / 7u; }
-
-__device__ __forceinline__ uint64_t entry_body_size(const ewal_entry &e) {
-  return 4 + eme_sov((uint64_t)(int64_t)e.type) + eme_sov(e.term) + eme_sov(e.index) + eme_sov(e.data_len) + e.data_len;
-}
+using ewal_wire::entry_size;
+using ewal_wire::sov;
 
 // fsz[i] = framed size of entry i, fsz[ne] = 0 (so that the exclusive sum's last element is the total)
 __global__ __launch_bounds__(256) void k_menc_esz(const ewal_entry *__restrict__ ents, uint64_t ne, uint64_t data_len,
@@ -88,8 +85,8 @@ __global__ __launch_bounds__(256) void k_menc_esz(const ewal_entry *__restrict__
     if (e.data_nil == 2 || e.data_len > data_len || e.data_off > data_len - e.data_len) {
       atomicOr(errflag, EME_ERR_RANGE);
     } else {
-      const uint64_t E = entry_body_size(e);
-      z = 1 + sov64(E) + E;
+      const uint64_t E = entry_size(e.type, e.term, e.index, e.data_len);
+      z = 1 + sov(E) + E;
     }
   }
   fsz[i] = z;
@@ -99,7 +96,7 @@ __global__ __launch_bounds__(256) void k_menc_usz(const uint64_t *__restrict__ u
                                                   uint64_t *__restrict__ usz) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i > nu) return;
-  usz[i] = i < nu ? 1 + sov64(u[i]) : 0;
+  usz[i] = i < nu ? 1 + sov(u[i]) : 0;
 }
 
 // Message regions, by their ends relative to the message's first byte:
@@ -115,16 +112,16 @@ __device__ __forceinline__ bool msg_layout(const emsg_out &m, const uint64_t *__
   const uint64_t eb = X[m.ents_first + m.n_ents] - X[m.ents_first];
   const uint64_t nb = NX[m.snap_nodes_off + m.snap_n_nodes] - NX[m.snap_nodes_off];
   const uint64_t rb = NX[m.snap_removed_off + m.snap_n_removed] - NX[m.snap_removed_off];
-  const uint64_t it = 2 + eme_sov(m.snap_index) + eme_sov(m.snap_term);
+  const uint64_t it = 2 + sov(m.snap_index) + sov(m.snap_term);
   bool ov = false;
-  uint64_t S = 1 + eme_sov(m.snap_data_len) + it;
+  uint64_t S = 1 + sov(m.snap_data_len) + it;
   ov |= __builtin_add_overflow(S, m.snap_data_len, &S);
   ov |= __builtin_add_overflow(S, nb, &S);
   ov |= __builtin_add_overflow(S, rb, &S);
   L.S = S;
-  L.e[0] = 6 + eme_sov(m.type) + eme_sov(m.to) + eme_sov(m.from) + eme_sov(m.term) + eme_sov(m.log_term) + eme_sov(m.index);
+  L.e[0] = 6 + sov(m.type) + sov(m.to) + sov(m.from) + sov(m.term) + sov(m.log_term) + sov(m.index);
   ov |= __builtin_add_overflow(L.e[0], eb, &L.e[1]);
-  ov |= __builtin_add_overflow(L.e[1], (uint64_t)(3 + eme_sov(m.commit) + eme_sov(S) + eme_sov(m.snap_data_len)), &L.e[2]);
+  ov |= __builtin_add_overflow(L.e[1], (uint64_t)(3 + sov(m.commit) + sov(S) + sov(m.snap_data_len)), &L.e[2]);
   ov |= __builtin_add_overflow(L.e[2], m.snap_data_len, &L.e[3]);
   ov |= __builtin_add_overflow(L.e[3], nb, &L.e[4]);
   ov |= __builtin_add_overflow(L.e[4], it, &L.e[5]);
@@ -228,7 +225,7 @@ struct EmeWin {
   }
   // tag v(value)
   __device__ __forceinline__ void fld(uint8_t tag, uint64_t v) {
-    const uint32_t s = 1 + eme_sov(v);
+    const uint32_t s = 1 + sov(v);
     if (skip >= s) { skip -= s; return; }
     if (full()) return;
     put(tag);
@@ -319,7 +316,7 @@ __device__ __forceinline__ void gen_run(const EmeArgs &a, uint64_t p, uint32_t w
         if (W.skip >= hdr) {
           W.skip -= hdr;
         } else {
-          W.fld(0x3a, entry_body_size(e));
+          W.fld(0x3a, entry_size(e.type, e.term, e.index, e.data_len));
           W.fld(0x08, (uint64_t)(int64_t)e.type); W.fld(0x10, e.term); W.fld(0x18, e.index);
           W.fld(0x22, e.data_len);
         }

@@ -19,6 +19,7 @@
 // No atomics; every output byte has exactly one writer.
 #include "ewal_device.h"
 #include "ewal_internal.h"
+#include "ewal_wire.h"
 
 #define ESS_TILE 32768u        // bytes of Data per tile (one wave); 2^ESS_TILE_LOG
 #define ESS_TILE_LOG 15
@@ -220,20 +221,13 @@ __global__ __launch_bounds__(ESS_FIN_THREADS) void k_snap_finish(const uint8_t *
   c = gshift_n(g_shift, f.tlen, c) ^ f.ltrail;
   const uint32_t crc = ~c;
   // snappb.Snapshot's header 08 v(crc) 12 v(blen), ending where the body starts
-  uint8_t h[17];
-  int hl = 0;
-  h[hl++] = 0x08;
-  for (uint32_t v = crc;; v >>= 7) {
-    if (v >= 0x80) { h[hl++] = (uint8_t)(v | 0x80); } else { h[hl++] = (uint8_t)v; break; }
-  }
-  h[hl++] = 0x12;
-  for (uint64_t v = f.blen;; v >>= 7) {
-    if (v >= 0x80) { h[hl++] = (uint8_t)(v | 0x80); } else { h[hl++] = (uint8_t)v; break; }
-  }
-  for (int k = 0; k < hl; ++k) out[f.body - hl + k] = h[k];
+  const uint64_t hl = 2 + ewal_wire::sov(crc) + ewal_wire::sov(f.blen);
+  uint8_t *p = out + f.body - hl;
+  *p++ = 0x08; p = ewal_wire::put_varint(p, crc);
+  *p++ = 0x12; ewal_wire::put_varint(p, f.blen);
   esnap_saved s;
   s.off = f.body - hl;
-  s.len = (uint64_t)hl + f.blen;
+  s.len = hl + f.blen;
   s.crc = crc;
   s.pad = 0;
   saved[blockIdx.x] = s;

@@ -678,6 +678,24 @@ class Encoder:
             pass
 
 
+def _write_device(ctx, fn, payload, arr, n, prev_crc, cap, *tail):
+    """One call of the batched write path: payload and the n records of arr to
+    the device, fn (ewal_encode_entries_device, or ewal_save_device with its
+    h_rec_off in tail), the frames back.  Returns (frame bytes, last CRC)."""
+    dd, dr, do = ctx.alloc(len(payload) + 64), ctx.alloc(C.sizeof(arr)), ctx.alloc(cap)
+    try:
+        if payload:
+            dd.upload(payload)
+        dr.upload(bytes(arr))
+        out_len, crc = C.c_uint64(), C.c_uint32()
+        check(fn(ctx.handle, dd.ptr, len(payload), dr.ptr, n, prev_crc, do.ptr, cap, C.byref(out_len), C.byref(crc),
+                 *tail))
+        return (do.download(out_len.value) if out_len.value else b""), crc.value
+    finally:
+        for b in (dd, dr, do):
+            b.free()
+
+
 def encode_entries_device(ctx: Context, entries, prev_crc: int = 0):
     """SaveEntry for every entry, in order, on the GPU (encoder.encode,
     wal/wal.go:248-263, wal/encoder.go:25-37): returns (frame bytes, the
@@ -692,19 +710,7 @@ def encode_entries_device(ctx: Context, entries, prev_crc: int = 0):
         arr[i].term, arr[i].index, arr[i].data_off, arr[i].data_len = e.Term, e.Index, off, len(d)
         arr[i].type, arr[i].data_nil = e.Type, int(e.Data is None)
         off += len(d)
-    cap = len(payload) + 80 * n + 64
-    dd, de, do = ctx.alloc(len(payload) + 64), ctx.alloc(C.sizeof(arr)), ctx.alloc(cap)
-    try:
-        if payload:
-            dd.upload(payload)
-        de.upload(bytes(arr))
-        out_len, crc = C.c_uint64(), C.c_uint32()
-        check(lib.ewal_encode_entries_device(ctx.handle, dd.ptr, len(payload), de.ptr, n, prev_crc, do.ptr, cap,
-                                             C.byref(out_len), C.byref(crc)))
-        return (do.download(out_len.value) if out_len.value else b""), crc.value
-    finally:
-        for b in (dd, de, do):
-            b.free()
+    return _write_device(ctx, lib.ewal_encode_entries_device, payload, arr, n, prev_crc, len(payload) + 80 * n + 64)
 
 
 def save_device(ctx: Context, ops, prev_crc: int = 0):
@@ -733,20 +739,9 @@ def save_device(ctx: Context, ops, prev_crc: int = 0):
         parts.append(d)
         off += len(d)
     payload = b"".join(parts)
-    cap = len(payload) + 120 * n + 64
-    dd, dr, do = ctx.alloc(len(payload) + 64), ctx.alloc(C.sizeof(arr)), ctx.alloc(cap)
-    try:
-        if payload:
-            dd.upload(payload)
-        dr.upload(bytes(arr))
-        out_len, crc = C.c_uint64(), C.c_uint32()
-        offs = (C.c_uint64 * max(1, n))()
-        check(lib.ewal_save_device(ctx.handle, dd.ptr, len(payload), dr.ptr, n, prev_crc, do.ptr, cap,
-                                   C.byref(out_len), C.byref(crc), offs))
-        return (do.download(out_len.value) if out_len.value else b""), crc.value, list(offs[:n])
-    finally:
-        for b in (dd, dr, do):
-            b.free()
+    offs = (C.c_uint64 * max(1, n))()
+    return _write_device(ctx, lib.ewal_save_device, payload, arr, n, prev_crc, len(payload) + 120 * n + 64, offs) + \
+        (list(offs[:n]),)
 
 
 def synth_wal(target_bytes, min_data=64, max_data=65536, seed=2, corrupt_record=-1, rewind_per_mille=0,

@@ -550,3 +550,99 @@ def test_encode_cases_cover_source_and_destination_alignments():
     assert pairs == {(a, b) for a in range(4) for b in range(4)}
     assert tail == {(s, L) for s in range(4) for L in range(4, 13)}      # misalignment 1, 2, 3 (and 0) at every length
     assert end_branch >= 20
+
+
+# ---------------------------------------------------------------------------
+# 5. write path: the two entry points over the one pipeline (k_wr_*)
+# ---------------------------------------------------------------------------
+WIRE_N = (1, 2, 63, 64, 65, 255, 256, 257)                    # around a wave's 64 lanes and a 256-thread block
+WIRE_TYPES = (0, 1, -1)
+WIRE_BOUNDS = tuple(v for k in range(1, 10) for v in ((1 << 7 * k) - 1, 1 << 7 * k))
+WIRE_DLENS = (None, 0, 1, 127, 128, 16383, 16384)
+
+
+def _wire_blob():
+    return make_pool(16384 + 256, seed=23).tobytes()
+
+
+def wire_entries(n, blob=None):
+    """n entries (type, term, index, data): Type over WIRE_TYPES, Term and
+    Index walking the varint width boundaries, Data over WIRE_DLENS."""
+    blob = blob or _wire_blob()
+    out = []
+    for i in range(n):
+        dl = WIRE_DLENS[i % len(WIRE_DLENS)]
+        data = None if dl is None else blob[i % 251:i % 251 + dl]
+        out.append((WIRE_TYPES[i % 3], WIRE_BOUNDS[i % 18], WIRE_BOUNDS[(7 * i + 3) % 18], data))
+    return out
+
+
+def test_wire_entries_cover_every_varint_width():
+    blob = _wire_blob()
+    for n in WIRE_N:
+        ents = wire_entries(n, blob)
+        assert len(ents) == n
+        if n < 63:      # 1 and 2 entries cannot hold ten widths: the coverage below is that of the six larger counts
+            continue
+        assert {_vlen(e[1]) for e in ents} == set(range(1, 11))           # Term
+        assert {_vlen(e[2]) for e in ents} == set(range(1, 11))           # Index
+        assert {_vlen(len(e[3] or b"")) for e in ents} == {1, 2, 3}       # len(Data)
+        assert {e[0] for e in ents} == set(WIRE_TYPES)
+        assert {None if e[3] is None else len(e[3]) for e in ents} == set(WIRE_DLENS)
+    # a negative Type is the 10-byte varint of its sign extension
+    assert O.entry_marshal(-1, 1, 1, None)[:11] == b"\x08" + b"\xff" * 9 + b"\x01"
+
+
+def stride_entries(cus):
+    """4 * 8 * cus + 5 entries of 0..3 Data bytes: five more than one trip of
+    the wave-per-record grid (8 workgroups of 4 waves on each of cus CUs)."""
+    return [(0, 1 + (i >> 12), i + 1, bytes([i & 0xff] * (i & 3))) for i in range(4 * 8 * cus + 5)]
+
+
+def test_stride_entries_exceed_one_grid_trip():
+    for cus in (1, 64, 256, 304):
+        ents = stride_entries(cus)
+        assert len(ents) == 4 * 8 * cus + 5 > 4 * 8 * cus
+        assert {len(e[3]) for e in ents} == {0, 1, 2, 3}
+
+
+def stream_len(ops):
+    """Bytes of the data-only stream of a save sequence: Entry and HardState
+    marshals and Cut metadata; an empty HardState writes nothing."""
+    x = 0
+    for kind, v in ops:
+        if kind == "cut":
+            x += len(v or b"")
+        elif kind == "state":
+            x += len(O.hardstate_marshal(*v)) if any(v) else 0
+        else:
+            x += len(O.entry_marshal(*v))
+    return x
+
+
+def empty_stream_sequences():
+    """Save sequences whose data-only stream is empty (E == 0)."""
+    st, cut = ("state", (0, 0, 0)), ("cut", None)
+    return [[st], [cut], [st, cut, st, cut]]
+
+
+def test_empty_stream_sequences_have_no_data_bytes():
+    for ops in empty_stream_sequences():
+        assert stream_len(ops) == 0
+    assert stream_len([("state", (0, 0, 1))]) == 6 and stream_len([("cut", b"")]) == 0
+    for prev in SAVE_PREVS:                    # the reference: an empty HardState leaves no frame
+        e = O.WalEncoder(prev)
+        e.save_state(0, 0, 0)
+        assert e.getvalue() == b"" and e.crc == prev
+
+
+def write_error_ranges(total):
+    """(data_off, data_len) outside a d_data of total bytes."""
+    return {"past_end": (total - 3, 4), "empty_past_end": (total + 1, 0)}
+
+
+def test_write_error_ranges_miss_by_one():
+    for total in (0 + 3, 100, 4096):
+        r = write_error_ranges(total)
+        assert sum(r["past_end"]) == total + 1 and r["past_end"][1] > 0
+        assert r["empty_past_end"] == (total + 1, 0)

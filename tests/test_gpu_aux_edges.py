@@ -313,3 +313,119 @@ def test_encode_entries_copy_alignments(ctx):
             assert crc.value == e.crc, total
     finally:
         dd.free()
+
+
+def _both_entry_points(ctx, ents, prev):
+    """ents through ewal_encode_entries_device and, as entry ops, through
+    ewal_save_device: both against the reference writer."""
+    ops = [("entry", W.Entry(*e)) for e in ents]
+    want, wcrc, woffs = _oracle_save(ops, prev)
+    got, crc = W.encode_entries_device(ctx, [x for _, x in ops], prev)
+    assert (len(got), crc) == (len(want), wcrc) and got == want, ("encode", len(ents), hex(prev))
+    got, crc, offs = W.save_device(ctx, ops, prev)
+    assert (len(got), crc) == (len(want), wcrc) and got == want, ("save", len(ents), hex(prev))
+    assert offs == woffs, ("save", len(ents), hex(prev))      # the running sum of the reference's frame sizes
+
+
+def test_write_entry_points_agree_at_varint_widths(ctx):
+    """Every Term / Index varint width, Type 0 / 1 / -1 and Data of None, 0 and
+    the 1 / 2 / 3-byte length boundaries, at record counts around a wave and a
+    block: one pipeline behind both entry points."""
+    blob = GEN._wire_blob()
+    for n in GEN.WIRE_N:
+        ents = GEN.wire_entries(n, blob)
+        for prev in GEN.SAVE_PREVS:
+            _both_entry_points(ctx, ents, prev)
+
+
+def test_write_grid_stride_second_trip(ctx):
+    """More records than one trip of the wave-per-record grid of k_wr_body /
+    k_wr_frame (4 waves x 8 workgroups x CUs)."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    ents = GEN.stride_entries(cus)
+    assert len(ents) > 4 * 8 * cus
+    _both_entry_points(ctx, ents, 0x9E3779B1)
+
+
+def test_save_empty_data_stream(ctx):
+    """E == 0: nothing but empty HardStates and nil-metadata Cuts -- no stream
+    pass, and the crcType / metadataType frames carry the running CRC."""
+    for seq in GEN.empty_stream_sequences():
+        ops = _ops(seq)
+        for prev in GEN.SAVE_PREVS:
+            assert W.save_device(ctx, ops, prev) == _oracle_save(ops, prev), ([k for k, _ in seq], hex(prev))
+
+
+def _raw_write(ctx, arr, n, payload, total, cap, prev=0x01234567):
+    """One raw call (ewal_save_device for SaveRec records, else
+    ewal_encode_entries_device) with d_out pre-filled with 0xA5: (status,
+    d_out's cap bytes, out_len, last_crc)."""
+    dd, dr, do = ctx.alloc(len(payload) + 64), ctx.alloc(C.sizeof(arr) + 64), ctx.alloc(cap + 64)
+    try:
+        dd.upload(payload)
+        dr.upload(bytes(arr))
+        do.upload(b"\xa5" * cap)
+        out_len, crc = C.c_uint64(77), C.c_uint32(77)
+        args = (ctx.handle, dd.ptr, total, dr.ptr, n, prev, do.ptr, cap, C.byref(out_len), C.byref(crc))
+        rc = L.lib.ewal_save_device(*args, None) if isinstance(arr[0], L.SaveRec) else \
+            L.lib.ewal_encode_entries_device(*args)
+        return rc, do.download(cap), out_len.value, crc.value
+    finally:
+        for b in (dd, dr, do):
+            b.free()
+
+
+def _recs(kind, ranges):
+    """Entries (Term 3, Index i + 1) over the (data_off, data_len) ranges, as
+    ewal_entry (kind "encode") or as ewal_save_rec entry records."""
+    arr = ((L.EntryDesc if kind == "encode" else L.SaveRec) * len(ranges))()
+    for i, (a, (off, ln)) in enumerate(zip(arr, ranges)):
+        a.data_off, a.data_len = off, ln
+        if kind == "encode":
+            a.term, a.index = 3, i + 1
+        else:
+            a.kind, a.a, a.b = L.SAVE_ENTRY, 3, i + 1
+    return arr
+
+
+@pytest.mark.parametrize("kind", ["encode", "save"])
+def test_write_errors_leave_the_output_untouched(ctx, kind):
+    """A payload one byte past d_data, an empty payload at data_len_total + 1
+    and a cap one byte short: the status, and not a byte of d_out written."""
+    prev, total = 0x01234567, 100
+    payload = bytes(range(total))
+    good = [(0, 10), (10, 0), (10, 90)]
+    e = O.WalEncoder(prev)
+    for i, (off, ln) in enumerate(good):
+        e.save_entry(0, 3, i + 1, payload[off:off + ln])
+    want = e.getvalue()
+    cap = len(want)
+    assert _raw_write(ctx, _recs(kind, good), 3, payload, total, cap, prev) == (0, want, cap, e.crc)
+    for name, rng in GEN.write_error_ranges(total).items():
+        for pos in (0, 1, 2):                                  # the record out of range: first, middle, last
+            ranges = good[:pos] + [rng] + good[pos + 1:]
+            assert _raw_write(ctx, _recs(kind, ranges), 3, payload, total, cap, prev) == \
+                (L.E_INVAL, b"\xa5" * cap, 0, prev), (name, pos)
+    assert _raw_write(ctx, _recs(kind, good), 3, payload, total, cap - 1, prev) == \
+        (L.E_NOMEM, b"\xa5" * (cap - 1), 0, prev)
+
+
+def test_save_unknown_kind_and_unread_ranges(ctx):
+    """An unknown kind is EWAL_E_INVAL; the data range of a HardState and of a
+    nil-metadata Cut is never read, so a wild one is not an error."""
+    prev, total = 0x9E3779B1, 16
+    payload = bytes(range(total))
+    arr = _recs("save", [(0, 4), (4, 12)])
+    arr[1].kind = 7
+    assert _raw_write(ctx, arr, 2, payload, total, 256, prev) == (L.E_INVAL, b"\xa5" * 256, 0, prev)
+    arr = (L.SaveRec * 3)()
+    arr[0].kind, arr[0].a, arr[0].b, arr[0].c = L.SAVE_STATE, 4, 2, 1 << 40
+    arr[1].kind, arr[1].data_nil = L.SAVE_CUT, 1
+    arr[2].kind, arr[2].a, arr[2].b, arr[2].data_off, arr[2].data_len = L.SAVE_ENTRY, 3, 1, 0, total
+    for a in arr[:2]:
+        a.data_off, a.data_len = (1 << 63) + 5, (1 << 62) + 1
+    ops = [("state", W.HardState(4, 2, 1 << 40)), ("cut", None), ("entry", W.Entry(0, 3, 1, payload))]
+    want, wcrc, _ = _oracle_save(ops, prev)
+    rc, out, out_len, crc = _raw_write(ctx, arr, 3, payload, total, 256, prev)
+    assert (rc, out_len, crc) == (0, len(want), wcrc) and out == want + b"\xa5" * (256 - len(want))
