@@ -139,6 +139,26 @@ class LeadResult(C.Structure):   # elead_result
 (LEAD_NOT_STEPPED, LEAD_IGNORED, LEAD_STEP_DOWN, LEAD_STALE, LEAD_PROBE, LEAD_UPDATED, LEAD_COMMITTED,
  LEAD_PANICKED) = range(8)
 
+
+class LeadPropState(C.Structure):   # elead_prop_state
+    _fields_ = [("ents_cap", C.c_uint64), ("unstable", C.c_uint64), ("pending_conf", C.c_uint64),
+                ("reserved", C.c_uint64)]
+
+
+class LeadLocal(C.Structure):   # elead_local
+    _fields_ = [("group", C.c_uint64), ("kind", C.c_uint64), ("etype", C.c_int32), ("data_nil", C.c_int32),
+                ("data_off", C.c_uint64), ("data_len", C.c_uint64), ("pad", C.c_uint64)]
+
+
+class LeadLocalResult(C.Structure):   # elead_local_result
+    _fields_ = [("status", C.c_int32), ("action", C.c_int32), ("msg_first", C.c_uint64), ("n_msgs", C.c_uint64),
+                ("index", C.c_uint64), ("ent_pos", C.c_uint64), ("committed", C.c_uint64)]
+
+
+# elead_local.kind, elead_local_result.action
+LEAD_L_MSG_BEAT, LEAD_L_MSG_PROP = 1, 2
+LEAD_L_NOT_STEPPED, LEAD_L_BEAT, LEAD_L_APPENDED, LEAD_L_DROPPED, LEAD_L_PANICKED = range(5)
+
 SNAP_FIELD_DATA, SNAP_FIELD_UNREC, SNAP_FIELD_NODES, SNAP_FIELD_REMOVED = range(4)
 SEG_UNREC, SEG_ENTRY_UNREC, SEG_ENTRY_DATA, SEG_SNAP_UNREC, SEG_SNAP_DATA, SEG_SNAP_NODE, SEG_SNAP_REMOVED = range(7)
 
@@ -350,6 +370,11 @@ _SIGS = {
     "elead_snap_size": (C.c_uint32, []),
     "elead_resp_size": (C.c_uint32, []),
     "elead_result_size": (C.c_uint32, []),
+    "elead_local_batch_device": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp,
+                                           vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "elead_prop_state_size": (C.c_uint32, []),
+    "elead_local_size": (C.c_uint32, []),
+    "elead_local_result_size": (C.c_uint32, []),
 }
 for _name, (_res, _args) in _SIGS.items():
     if os.environ.get("EWAL_LIB_PATH") and not hasattr(lib, _name):

@@ -34,6 +34,7 @@
 #include "msg_encode.hip"
 #include "log_append.hip"
 #include "lead_step.hip"
+#include "lead_prop.hip"
 #include "ewal_stage.h"
 #include "ewal_wire.h"
 
@@ -191,6 +192,10 @@ struct ewal_ctx {
   // batched leader msgAppResp step (elead_step_batch_device): head words, the
   // groups' claims, the runs' message counts, per-workgroup partial sums
   DevBuf lead;
+  // batched leader msgProp / msgBeat step (elead_local_batch_device): head
+  // words, the groups' claims, the records' segment counts and message
+  // counts, per-workgroup segment aggregates and partial sums
+  DevBuf lprop;
   std::vector<uint64_t> bent_first, bnents;   // per shard: first ent in bents, count
   std::vector<std::vector<ewal_unrec>> bunrec;       // per shard replayed alone: its XXX_unrecognized side list
   std::vector<std::vector<uint8_t>> bunrec_bytes;
@@ -3481,6 +3486,85 @@ int elead_step_batch_device(ewal_ctx *c, elead_group *d_groups, uint64_t G, cons
   EW_CHECK(hipStreamSynchronize(c->stream));
   if (n_msgs) *n_msgs = h.n_msgs;
   if (n_committed) *n_committed = h.n_committed;
+  return EWAL_OK;
+}
+
+uint32_t elead_prop_state_size(void) { return sizeof(elead_prop_state); }
+uint32_t elead_local_size(void) { return sizeof(elead_local); }
+uint32_t elead_local_result_size(void) { return sizeof(elead_local_result); }
+
+static_assert(sizeof(elead_prop_state) == 32 && sizeof(elead_local) == 48 && sizeof(elead_local_result) == 48 &&
+                  offsetof(elead_local, data_off) == 24 && offsetof(elead_local_result, index) == 24 &&
+                  offsetof(elead_group, nlog) == 32,
+              "elead_local layout");
+int elead_local_batch_device(ewal_ctx *c, elead_group *d_groups, elead_prop_state *d_state, uint64_t G,
+                             const elead_snap *d_snaps, ewal_entry *d_ents, uint64_t n_ents_total,
+                             uint64_t data_len_total, const elead_local *d_locals, uint64_t n,
+                             elead_local_result *d_res, emsg_out *d_msgs, uint64_t msgs_cap, uint64_t *n_msgs,
+                             uint64_t *n_appended) {
+  if (n_msgs) *n_msgs = 0;
+  if (n_appended) *n_appended = 0;
+  if (!c) return EWAL_E_INVAL;
+  if (n >= 0x7fffffffull || G >= 0x7fffffffull) return EWAL_E_INVAL;
+  if (n == 0) return EWAL_OK;
+  if (!d_groups || !d_state || !d_locals || !d_res || (n_ents_total && !d_ents)) return EWAL_E_INVAL;
+  if ((((uintptr_t)d_groups | (uintptr_t)d_state | (uintptr_t)d_snaps | (uintptr_t)d_locals | (uintptr_t)d_res |
+        (uintptr_t)d_msgs) &
+       15) != 0 ||
+      ((uintptr_t)d_ents & 7) != 0)
+    return EWAL_E_INVAL;
+  EW_CHECK(hipSetDevice(c->device));
+  forget_records(c);
+  // scratch: head | claim[G] | seg[n] | cnt[n] | agg[workgroups] | partial[2 * workgroups]
+  const uint32_t blocks = grid_for(n, 256);
+  const size_t o_claim = 64, o_seg = (o_claim + (size_t)G * 4 + 15) & ~(size_t)15, o_cnt = o_seg + (size_t)n * 8,
+               o_agg = (o_cnt + (size_t)n * 8 + 15) & ~(size_t)15, o_part = o_agg + (size_t)blocks * 16;
+  EW_CHECK(c->lprop.ensure(o_part + (size_t)blocks * 16));
+  uint8_t *base = c->lprop.as<uint8_t>();
+  EpropArgs a;
+  a.groups = d_groups;
+  a.state = d_state;
+  a.G = G;
+  a.snaps = d_snaps;
+  a.ents = d_ents;
+  a.n_ents_total = n_ents_total;
+  a.data_len_total = data_len_total;
+  a.locals = d_locals;
+  a.n = n;
+  a.res = d_res;
+  a.msgs = d_msgs;
+  a.head = (EleadHead *)base;
+  a.claim = (uint32_t *)(base + o_claim);
+  a.seg = (unsigned long long *)(base + o_seg);
+  a.cnt = (unsigned long long *)(base + o_cnt);
+  a.agg = (EpropAgg *)(base + o_agg);
+  a.partial = (unsigned long long *)(base + o_part);
+  EW_CHECK(hipEventRecord(c->ev0, c->stream));
+  EW_CHECK(hipMemsetAsync(a.head, 0, sizeof(EleadHead), c->stream));
+  if (G) EW_CHECK(hipMemsetAsync(a.claim, 0xff, (size_t)G * 4, c->stream));
+  hipLaunchKernelGGL(k_prop_check, dim3(blocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_prop_carry, dim3(1), dim3(256), 0, c->stream, a.agg, blocks);
+  hipLaunchKernelGGL(k_prop_count, dim3(blocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.partial, blocks, a.head);
+  EW_CHECK(hipGetLastError());
+  // the one decision point: nothing of the caller's has been modified yet
+  EleadHead h;
+  EW_CHECK(hipMemcpyAsync(&h, a.head, sizeof(EleadHead), hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  if (h.errflag & EPROP_ERR_INVAL) return EWAL_E_INVAL;
+  if (h.errflag & EPROP_ERR_NOMEM) return EWAL_E_NOMEM;
+  if (d_msgs && h.n_msgs > msgs_cap) return EWAL_E_NOMEM;
+  if (d_msgs) {
+    hipLaunchKernelGGL(k_prop_apply<true>, dim3(blocks), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(k_prop_commit, dim3(blocks), dim3(256), 0, c->stream, a);
+  } else {
+    hipLaunchKernelGGL(k_prop_apply<false>, dim3(blocks), dim3(256), 0, c->stream, a);
+  }
+  EW_CHECK(hipGetLastError());
+  EW_CHECK(hipEventRecord(c->ev1, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  if (n_msgs) *n_msgs = h.n_msgs;
+  if (n_appended) *n_appended = h.n_committed;
   return EWAL_OK;
 }
 

@@ -936,6 +936,121 @@ uint32_t elead_snap_size(void);
 uint32_t elead_resp_size(void);
 uint32_t elead_result_size(void);
 
+/* ---- leader msgProp / msgBeat step: stepLeader's msgProp and msgBeat cases,
+ * raft/raft.go:441-455.  Batched over n local messages for the leaders of G
+ * raft groups -- the step that starts a replication round: appendEntry
+ * (:279-285) with raftLog.append (raft/log.go:71-75), progress.update
+ * (:71-74) and maybeCommit (:248-258), then bcastAppend (:229-236); and
+ * bcastHeartbeat / sendHeartbeat (:219-226, :238-246).  Client proposals and
+ * heartbeat ticks come in; the grown log (d_ents is WRITTEN here, and only
+ * here), progress, commit and the fan-out's emsg_out records come out.  The
+ * groups are elead_step_batch_device's elead_group records, unchanged, so the
+ * same array feeds both calls; what a proposal needs beyond them lives in a
+ * side array.  All arithmetic is Go's uint64 and wraps. */
+typedef struct elead_prop_state {   /* 32 bytes; a DEVICE array of G, updated in place */
+  uint64_t ents_cap;      /* room at elead_group.ents_first, in entries (>= nlog) */
+  uint64_t unstable;      /* raftLog.unstable                        (updated) */
+  uint64_t pending_conf;  /* raft.pendingConf, 0 or 1                (updated) */
+  uint64_t reserved;      /* 0 */
+} elead_prop_state;
+typedef struct elead_local {        /* 48 bytes; one local message; a DEVICE array of n */
+  uint64_t group;                   /* which elead_group steps it */
+  uint64_t kind;                    /* 1 = msgBeat, 2 = msgProp (raft.go:17-27) */
+  int32_t etype, data_nil;          /* msgProp: Entries[0].Type, and whether Data is nil */
+  uint64_t data_off, data_len;      /* Entries[0].Data = d_data[data_off, + data_len) */
+  uint64_t pad;
+} elead_local;
+enum { ELEAD_L_NOT_STEPPED = 0,     /* after a panic in its group's run: the caller's to step */
+       ELEAD_L_BEAT = 1,            /* msgBeat: bcastHeartbeat */
+       ELEAD_L_APPENDED = 2,        /* msgProp: appendEntry, bcastAppend */
+       ELEAD_L_DROPPED = 3,         /* msgProp: a ConfChange while pendingConf */
+       ELEAD_L_PANICKED = 4 };      /* Go panics (status says where), or the group is unsupported */
+typedef struct elead_local_result { /* 48 bytes; a DEVICE array of n */
+  int32_t status, action;           /* EWAL_OK, an EWAL_PANIC_ class, EWAL_UNSUPPORTED_ENCODING; ELEAD_L_* */
+  uint64_t msg_first, n_msgs;       /* its messages: d_msgs[msg_first, + n_msgs) */
+  uint64_t index;                   /* the Index given to the entry (0 unless APPENDED) */
+  uint64_t ent_pos;                 /* where it was written in d_ents   (0 unless APPENDED) */
+  uint64_t committed;               /* raftLog.committed after this record */
+} elead_local_result;
+/* Order, output placement, the size query (d_msgs == NULL), the stream, the
+ * timing and the allocation rule are elead_step_batch_device's, with "record"
+ * for "response": a group's records are adjacent and stepped in array order,
+ * runs have any length and lie anywhere, the messages are dense and ordered by
+ * record, then by peer slot, msg_first counts the messages of the records
+ * before i also when n_msgs == 0, and no emsg_out at or past *n_msgs is
+ * written.  *n_appended = the ELEAD_L_APPENDED records (nullable, as *n_msgs).
+ * Proposals carry Term == 0 (send, raft.go:190-199), so Step's term switch is
+ * "local message"; removed[] / msgDenied routing stays the caller's.
+ * Per record:
+ *   kind 1 (msgBeat): one emsg_out per peer slot whose peer_id != id, in slot
+ *     order: type = 3 (sendHeartbeat's empty msgApp), to, from = id, term =
+ *     group.term, every other field 0.  ELEAD_L_BEAT; nothing else changes.
+ *   kind 2 (msgProp), e = Entries[0]:
+ *     etype == 1 (EntryConfChange) while pending_conf != 0: ELEAD_L_DROPPED,
+ *       nothing else happens.  Otherwise a ConfChange sets pending_conf = 1.
+ *     appendEntry: e.Term = group.term, e.Index = lastIndex() + 1 (lastIndex =
+ *       nlog - 1 + log_offset).  raftLog.append(lastIndex(), e) is ents =
+ *       append(slice(log_offset, lastIndex() + 1), e): where that slice is nil
+ *       -- an empty log, or nlog - 1 + log_offset or lastIndex() + 1 wrapping
+ *       -- THE LOG BECOMES THE ONE NEW ENTRY (nlog = 1), as in Go; otherwise
+ *       nlog grows by one.  unstable = min(unstable, e.Index).  Then
+ *       prs[id].update(lastIndex()) and maybeCommit, as in
+ *       elead_step_batch_device, its result ignored.
+ *     bcastAppend, always: one sendAppend per peer slot whose peer_id != id,
+ *       in slot order, bit for bit the records elead_step_batch_device
+ *       documents (msgSnap from d_snaps, log_term, commit, and the ents_first /
+ *       n_ents range, which now ends with the new entry).  ELEAD_L_APPENDED.
+ *     The entry is stored at d_ents[ents_first + k], k its position in the new
+ *       log: {term, index, data_off, data_len, type = etype, data_nil};
+ *       d_res[i].index and .ent_pos (= ents_first + k) name it.
+ * Written: of a named group committed, nlog, match[] and next[] (of prs[id]
+ * only); of its state record unstable and pending_conf; the appended d_ents
+ * slots; d_res; d_msgs below *n_msgs.  Nothing of a group that no record
+ * names, and no entry of the log as the call found it, except slot 0 in the
+ * nil-slice case above.
+ * Where Go panics the record gets a status:
+ *   EWAL_PANIC_NIL_PROGRESS   a proposal for a group whose id is not among
+ *                             the first n_peers peer_id (prs[r.id] is nil)
+ *   EWAL_PANIC_NEED_SNAPSHOT, EWAL_PANIC_FIRST_ENTRY, EWAL_PANIC_BOUNDS
+ *                             in the broadcast or in maybeCommit's term(), as
+ *                             in elead_step_batch_device
+ * and the first record (of either kind) of a group with n_peers > 7 gets
+ * EWAL_UNSUPPORTED_ENCODING in the same way.  Such a record -- wherever it
+ * panics, the k-th message of the broadcast included -- has action
+ * ELEAD_L_PANICKED, emits nothing, leaves the group record, the state record
+ * and d_ents exactly as they were before that record, reports the unchanged
+ * committed, and puts the rest of its group's run at ELEAD_L_NOT_STEPPED.
+ * Records stepped before it keep their effect.  A msgBeat cannot panic.
+ * Checked on the device before anything is modified (then d_groups, d_state,
+ * d_ents, d_res and d_msgs are untouched and the counters are 0):
+ *   EWAL_E_INVAL  group >= G; a group's records not adjacent; kind not 1 or 2;
+ *                 data_nil not 0 or 1 (either kind); a proposal's Data range
+ *                 outside data_len_total, or wrapping; and of a named group:
+ *                 ents_first + ents_cap outside n_ents_total, or wrapping;
+ *                 nlog > ents_cap; two equal peer_id within the first
+ *                 min(n_peers, 7) slots; reserved != 0 in the group or the
+ *                 state record; pending_conf > 1
+ *   EWAL_E_NOMEM  a named group has nlog + (the kind-2 records of its run) >
+ *                 ents_cap (dropped proposals count: the room is decided
+ *                 before any is stepped); or the messages exceed msgs_cap
+ *                 (INVAL wins when both occur in one call)
+ * and on the host as in elead_step_batch_device, d_state sharing d_groups'
+ * rules.  n == 0: EWAL_OK, counters 0.
+ * The entry windows [ents_first, + ents_cap) of the named groups must not
+ * overlap each other: the caller's contract, not checked.  The free slots of
+ * a window are never read here, but emsg_encode_batch_device checks every
+ * entry of the d_ents it is given: keep them zero when d_ents goes there. */
+int elead_local_batch_device(ewal_ctx *ctx, elead_group *d_groups, elead_prop_state *d_state, uint64_t G,
+                             const elead_snap *d_snaps /* G, nullable */,
+                             ewal_entry *d_ents, uint64_t n_ents_total, uint64_t data_len_total,
+                             const elead_local *d_locals, uint64_t n, elead_local_result *d_res,
+                             struct emsg_out *d_msgs /* NULL: size query */, uint64_t msgs_cap,
+                             uint64_t *n_msgs, uint64_t *n_appended);
+/* For bindings / tests: the sizes of the three records. */
+uint32_t elead_prop_state_size(void);
+uint32_t elead_local_size(void);
+uint32_t elead_local_result_size(void);
+
 /* ---- raft ingress: raftpb.Message.Unmarshal, raft/raftpb/raft.pb.go:407-617
  * (called per POST /raft in etcdserver/etcdhttp/http.go:119-146), batched
  * over n messages resident in one device buffer at offs[i], lens[i] (host
