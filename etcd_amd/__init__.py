@@ -9,6 +9,7 @@ Product layout:
   raftlog.py   batched `raft.handleAppendEntries` / `raftLog.maybeAppend` (the follower's append)
   raftlead.py  batched `stepLeader` msgAppResp case (the leader's progress, commit and next fan-out)
   raftprop.py  batched `stepLeader` msgProp / msgBeat cases (the leader's append and the round's first fan-out)
+  raftvote.py  batched election step: msgHup / msgVote / msgVoteResp (campaign, the vote, poll, becomeLeader)
   crc.py       `pkg/crc` digest (chained CRC-32C) over host or device buffers
   raftmsg.py   batched `raftpb.Message` decode (the /raft ingress) and Marshal (the egress)
   shard.py     per-rank shard assignment, the RCCL summary all-reduce and the
@@ -21,7 +22,8 @@ from .snap import save_packed, save_dir, snap_name  # noqa: F401
 from .raftlog import append_batch, append_batch_device  # noqa: F401
 from .raftlead import lead_step_batch, lead_step_batch_device  # noqa: F401
 from .raftprop import local_batch, local_batch_device  # noqa: F401
+from .raftvote import vote_batch, vote_batch_device  # noqa: F401
 
 __all__ = ["Context", "OpenAtIndex", "Create", "Encoder", "readall_bytes", "synth_wal", "save_packed", "save_dir",
            "snap_name", "append_batch", "append_batch_device", "lead_step_batch", "lead_step_batch_device",
-           "local_batch", "local_batch_device"]
+           "local_batch", "local_batch_device", "vote_batch", "vote_batch_device"]

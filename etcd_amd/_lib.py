@@ -54,6 +54,9 @@ PANIC_COMMITTED_CONFLICT = 38
 PANIC_NIL_PROGRESS = 39
 PANIC_NEED_SNAPSHOT = 40
 PANIC_FIRST_ENTRY = 41
+PANIC_LEADER_TO_CANDIDATE = 42
+PANIC_NIL_ENTRY = 43
+PANIC_DOUBLE_CONF = 44
 UNSUPPORTED_ENCODING = 48
 E_HIP, E_INVAL, E_NOMEM, E_NODEVICE, E_TIMEOUT, E_IO = -1, -2, -3, -4, -5, -6
 
@@ -158,6 +161,29 @@ class LeadLocalResult(C.Structure):   # elead_local_result
 # elead_local.kind, elead_local_result.action
 LEAD_L_MSG_BEAT, LEAD_L_MSG_PROP = 1, 2
 LEAD_L_NOT_STEPPED, LEAD_L_BEAT, LEAD_L_APPENDED, LEAD_L_DROPPED, LEAD_L_PANICKED = range(5)
+
+
+class VoteState(C.Structure):   # evote_state
+    _fields_ = [("state", C.c_uint64), ("vote", C.c_uint64), ("lead", C.c_uint64), ("elapsed", C.c_uint64),
+                ("voted", C.c_uint64), ("granted", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+
+class VoteMsg(C.Structure):   # evote_msg
+    _fields_ = [("group", C.c_uint64), ("kind", C.c_uint64), ("from_", C.c_uint64), ("term", C.c_uint64),
+                ("index", C.c_uint64), ("log_term", C.c_uint64), ("reject", C.c_int32), ("pad", C.c_int32),
+                ("pad2", C.c_uint64)]
+
+
+class VoteResult(C.Structure):   # evote_result
+    _fields_ = [("status", C.c_int32), ("action", C.c_int32), ("msg_first", C.c_uint64), ("n_msgs", C.c_uint64),
+                ("term", C.c_uint64), ("vote", C.c_uint64), ("state", C.c_int32), ("flags", C.c_int32)]
+
+
+# evote_msg.kind, evote_state.state, evote_result.action
+VOTE_MSG_HUP, VOTE_MSG_VOTE, VOTE_MSG_VOTE_RESP = 0, 5, 6
+VOTE_FOLLOWER, VOTE_CANDIDATE, VOTE_LEADER = range(3)
+(VOTE_NOT_STEPPED, VOTE_IGNORED, VOTE_GRANTED, VOTE_REJECTED, VOTE_CAMPAIGNED, VOTE_WON, VOTE_LOST, VOTE_POLLED,
+ VOTE_NO_CASE, VOTE_PANICKED) = range(10)
 
 SNAP_FIELD_DATA, SNAP_FIELD_UNREC, SNAP_FIELD_NODES, SNAP_FIELD_REMOVED = range(4)
 SEG_UNREC, SEG_ENTRY_UNREC, SEG_ENTRY_DATA, SEG_SNAP_UNREC, SEG_SNAP_DATA, SEG_SNAP_NODE, SEG_SNAP_REMOVED = range(7)
@@ -375,6 +401,11 @@ _SIGS = {
     "elead_prop_state_size": (C.c_uint32, []),
     "elead_local_size": (C.c_uint32, []),
     "elead_local_result_size": (C.c_uint32, []),
+    "evote_step_batch_device": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp,
+                                          C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "evote_state_size": (C.c_uint32, []),
+    "evote_msg_size": (C.c_uint32, []),
+    "evote_result_size": (C.c_uint32, []),
 }
 for _name, (_res, _args) in _SIGS.items():
     if os.environ.get("EWAL_LIB_PATH") and not hasattr(lib, _name):
@@ -406,7 +437,7 @@ def header_symbols(path=HEADER):
     """Every function declared in include/ewal.h."""
     txt = open(path).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead)_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead|vote)_[a-z0-9_]+)\s*\(", txt)))
 
 
 def status_string(st):
@@ -437,6 +468,6 @@ def check(st, detail=0, record=-1, offset=-1):
         return
     if st == E_NODEVICE:
         raise NoDeviceError(st)
-    if 32 <= st <= 41:
+    if 32 <= st <= 44:
         raise GoPanic(st, detail, record, offset)
     raise EwalError(st, detail, record, offset)

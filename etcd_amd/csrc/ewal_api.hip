@@ -35,6 +35,7 @@
 #include "log_append.hip"
 #include "lead_step.hip"
 #include "lead_prop.hip"
+#include "vote_step.hip"
 #include "ewal_stage.h"
 #include "ewal_wire.h"
 
@@ -196,6 +197,10 @@ struct ewal_ctx {
   // words, the groups' claims, the records' segment counts and message
   // counts, per-workgroup segment aggregates and partial sums
   DevBuf lprop;
+  // batched election step (evote_step_batch_device): head words, the groups'
+  // claims, the terms of the runs' own entries, the runs' message counts,
+  // per-workgroup partial sums
+  DevBuf lvote;
   std::vector<uint64_t> bent_first, bnents;   // per shard: first ent in bents, count
   std::vector<std::vector<ewal_unrec>> bunrec;       // per shard replayed alone: its XXX_unrecognized side list
   std::vector<std::vector<uint8_t>> bunrec_bytes;
@@ -3565,6 +3570,80 @@ int elead_local_batch_device(ewal_ctx *c, elead_group *d_groups, elead_prop_stat
   EW_CHECK(hipStreamSynchronize(c->stream));
   if (n_msgs) *n_msgs = h.n_msgs;
   if (n_appended) *n_appended = h.n_committed;
+  return EWAL_OK;
+}
+
+uint32_t evote_state_size(void) { return sizeof(evote_state); }
+uint32_t evote_msg_size(void) { return sizeof(evote_msg); }
+uint32_t evote_result_size(void) { return sizeof(evote_result); }
+
+static_assert(sizeof(evote_state) == 64 && sizeof(evote_msg) == 64 && sizeof(evote_result) == 48 &&
+                  offsetof(evote_state, voted) == 32 && offsetof(evote_msg, reject) == 48 &&
+                  offsetof(evote_result, term) == 24 && offsetof(evote_result, state) == 40,
+              "evote_step layout");
+int evote_step_batch_device(ewal_ctx *c, elead_group *d_groups, elead_prop_state *d_pstate, evote_state *d_vstate,
+                            uint64_t G, const elead_snap *d_snaps, ewal_entry *d_ents, uint64_t n_ents_total,
+                            const evote_msg *d_in, uint64_t n, evote_result *d_res, emsg_out *d_msgs,
+                            uint64_t msgs_cap, uint64_t *n_msgs, uint64_t *n_won) {
+  if (n_msgs) *n_msgs = 0;
+  if (n_won) *n_won = 0;
+  if (!c) return EWAL_E_INVAL;
+  if (n >= 0x7fffffffull || G >= 0x7fffffffull) return EWAL_E_INVAL;
+  if (n == 0) return EWAL_OK;
+  if (!d_groups || !d_pstate || !d_vstate || !d_in || !d_res || (n_ents_total && !d_ents)) return EWAL_E_INVAL;
+  if ((((uintptr_t)d_groups | (uintptr_t)d_pstate | (uintptr_t)d_vstate | (uintptr_t)d_snaps | (uintptr_t)d_in |
+        (uintptr_t)d_res | (uintptr_t)d_msgs) &
+       15) != 0 ||
+      ((uintptr_t)d_ents & 7) != 0)
+    return EWAL_E_INVAL;
+  EW_CHECK(hipSetDevice(c->device));
+  forget_records(c);
+  // scratch: head | claim[G] | fterm[n] | run_msgs[n] | partial[2 * workgroups]
+  const uint32_t blocks = grid_for(n, 256);
+  const size_t o_claim = 64, o_ft = (o_claim + (size_t)G * 4 + 15) & ~(size_t)15, o_run = o_ft + (size_t)n * 8,
+               o_part = (o_run + (size_t)n * 8 + 15) & ~(size_t)15;
+  EW_CHECK(c->lvote.ensure(o_part + (size_t)blocks * 16));
+  uint8_t *base = c->lvote.as<uint8_t>();
+  EvoteArgs a{};
+  a.p.groups = d_groups;
+  a.p.state = d_pstate;
+  a.p.G = G;
+  a.p.snaps = d_snaps;
+  a.p.ents = d_ents;
+  a.p.n_ents_total = n_ents_total;
+  a.p.n = n;
+  a.p.msgs = d_msgs;
+  a.p.head = (EleadHead *)base;
+  a.p.claim = (uint32_t *)(base + o_claim);
+  a.p.partial = (unsigned long long *)(base + o_part);
+  a.vstate = d_vstate;
+  a.in = d_in;
+  a.n = n;
+  a.res = d_res;
+  a.fterm = (unsigned long long *)(base + o_ft);
+  a.run_msgs = (unsigned long long *)(base + o_run);
+  EW_CHECK(hipEventRecord(c->ev0, c->stream));
+  EW_CHECK(hipMemsetAsync(a.p.head, 0, sizeof(EleadHead), c->stream));
+  if (G) EW_CHECK(hipMemsetAsync(a.p.claim, 0xff, (size_t)G * 4, c->stream));
+  hipLaunchKernelGGL(k_vote_count, dim3(blocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.p.partial, blocks, a.p.head);
+  EW_CHECK(hipGetLastError());
+  // the one decision point: nothing of the caller's has been modified yet
+  EleadHead h;
+  EW_CHECK(hipMemcpyAsync(&h, a.p.head, sizeof(EleadHead), hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  if (h.errflag & EVOTE_ERR_INVAL) return EWAL_E_INVAL;
+  if (h.errflag & EVOTE_ERR_NOMEM) return EWAL_E_NOMEM;
+  if (d_msgs && h.n_msgs > msgs_cap) return EWAL_E_NOMEM;
+  if (d_msgs)
+    hipLaunchKernelGGL(k_vote_apply<true>, dim3(blocks), dim3(256), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(k_vote_apply<false>, dim3(blocks), dim3(256), 0, c->stream, a);
+  EW_CHECK(hipGetLastError());
+  EW_CHECK(hipEventRecord(c->ev1, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  if (n_msgs) *n_msgs = h.n_msgs;
+  if (n_won) *n_won = h.n_committed;
   return EWAL_OK;
 }
 

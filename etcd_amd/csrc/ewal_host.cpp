@@ -322,6 +322,9 @@ const char *ewal_status_string(int st) {
   case EWAL_PANIC_NIL_PROGRESS: return "panic: nil progress (message from an unknown peer)";
   case EWAL_PANIC_NEED_SNAPSHOT: return "panic: need non-empty snapshot";
   case EWAL_PANIC_FIRST_ENTRY: return "panic: cannot return the first entry in log";
+  case EWAL_PANIC_LEADER_TO_CANDIDATE: return "panic: invalid transition [leader -> candidate]";
+  case EWAL_PANIC_NIL_ENTRY: return "panic: nil entry (isUpToDate on an empty log)";
+  case EWAL_PANIC_DOUBLE_CONF: return "panic: unexpected double uncommitted config entry";
   case EWAL_UNSUPPORTED_ENCODING: return "unsupported (non-canonical) record encoding";
   case EWAL_E_HIP: return "HIP error";
   case EWAL_E_INVAL: return "invalid argument";

@@ -48,6 +48,9 @@ enum {
   EWAL_PANIC_NIL_PROGRESS = 39,    /* r.prs[m.From] is nil and is dereferenced, raft/raft.go:458,462 */
   EWAL_PANIC_NEED_SNAPSHOT = 40,   /* panic("need non-empty snapshot"), raft/raft.go:559 */
   EWAL_PANIC_FIRST_ENTRY = 41,     /* panic("cannot return the first entry in log"), raft/log.go:131 */
+  EWAL_PANIC_LEADER_TO_CANDIDATE = 42, /* panic("invalid transition [leader -> candidate]"), raft/raft.go:320 */
+  EWAL_PANIC_NIL_ENTRY = 43,       /* at(lastIndex()) is nil and is dereferenced, raft/log.go:137-138 */
+  EWAL_PANIC_DOUBLE_CONF = 44,     /* panic("unexpected double uncommitted config entry"), raft/raft.go:344 */
   EWAL_UNSUPPORTED_ENCODING = 48,  /* protobuf groups nested deeper than the device
                                       walker's stack; reported, never guessed */
   /* infrastructure (negative) */
@@ -1050,6 +1053,150 @@ int elead_local_batch_device(ewal_ctx *ctx, elead_group *d_groups, elead_prop_st
 uint32_t elead_prop_state_size(void);
 uint32_t elead_local_size(void);
 uint32_t elead_local_result_size(void);
+
+/* ---- election step: raft.Step for msgHup, msgVote and msgVoteResp,
+ * raft/raft.go:372-408.  Batched over n election messages for G raft groups --
+ * the round that gives a restarted host its leaders: the msgVote case of
+ * stepFollower / stepCandidate / stepLeader (:467-468, :482-483, :511-518),
+ * stepCandidate's msgVoteResp case (:484-492), campaign (:358-370), poll
+ * (:177-187), reset (:260-273), becomeFollower / becomeCandidate / becomeLeader
+ * (:309-349) and raftLog.isUpToDate (raft/log.go:136-139).  A group is its
+ * elead_group plus its elead_prop_state, both unchanged (the same arrays feed
+ * the three leader-side calls; elead_group.reserved stays 0), plus the side
+ * record below.  becomeLeader's empty entry is appended to d_ents and the
+ * winner's bcastAppend comes out as emsg_out records, as
+ * elead_local_batch_device would write them; msgVote and msgVoteResp come out
+ * as emsg_out records too.  All arithmetic is Go's uint64 and wraps; None is 0. */
+typedef struct evote_state {        /* 64 bytes; a DEVICE array of G, updated in place */
+  uint64_t state;                   /* raft.state: 0 follower, 1 candidate, 2 leader (Go's StateType) */
+  uint64_t vote;                    /* HardState.Vote */
+  uint64_t lead;                    /* raft.lead */
+  uint64_t elapsed;                 /* raft.elapsed */
+  uint64_t voted;                   /* bit s: r.votes has the key peer_id[s] */
+  uint64_t granted;                 /* bit s: that value is true (a subset of voted) */
+  uint64_t reserved[2];             /* 0 */
+} evote_state;
+typedef struct evote_msg {          /* 64 bytes; one message; a DEVICE array of n */
+  uint64_t group;                   /* which group steps it */
+  uint64_t kind;                    /* 0 = msgHup, 5 = msgVote, 6 = msgVoteResp (raft.go:17-34) */
+  uint64_t from, term, index, log_term;   /* m.From, m.Term, m.Index, m.LogTerm */
+  int32_t reject, pad;              /* m.Reject; 0 */
+  uint64_t pad2;                    /* 0 */
+} evote_msg;
+enum { EVOTE_NOT_STEPPED = 0,       /* after a panic in its group's run: the caller's to step */
+       EVOTE_IGNORED = 1,           /* 0 < m.Term < r.Term */
+       EVOTE_GRANTED = 2,           /* msgVote: the vote was granted */
+       EVOTE_REJECTED = 3,          /* msgVote: a rejecting msgVoteResp was sent */
+       EVOTE_CAMPAIGNED = 4,        /* msgHup: became candidate, msgVote sent */
+       EVOTE_WON = 5,               /* became leader */
+       EVOTE_LOST = 6,              /* the rejecting quorum: becomeFollower(r.Term, None) */
+       EVOTE_POLLED = 7,            /* msgVoteResp counted, no decision */
+       EVOTE_NO_CASE = 8,           /* msgVoteResp at a follower or leader: the step function has no case */
+       EVOTE_PANICKED = 9 };        /* Go panics (status says where), or the record is unsupported */
+typedef struct evote_result {       /* 48 bytes; a DEVICE array of n */
+  int32_t status, action;           /* EWAL_OK, an EWAL_PANIC_ class, EWAL_UNSUPPORTED_ENCODING; EVOTE_* */
+  uint64_t msg_first, n_msgs;       /* its messages: d_msgs[msg_first, + n_msgs) */
+  uint64_t term, vote;              /* raft.Term and Vote after this record */
+  int32_t state;                    /* raft.state after this record */
+  int32_t flags;                    /* bit 0: Step's term switch ran becomeFollower before the case */
+} evote_result;
+/* Order, output placement, the size query (d_msgs == NULL), the stream, the
+ * timing and the allocation rule are elead_step_batch_device's, with "record"
+ * for "response": a group's records are adjacent and stepped in array order,
+ * each one seeing the state the previous one left (two candidates' msgVote in
+ * one run is the normal case), runs have any length and lie anywhere, the
+ * messages are dense and ordered by record, then by peer slot, msg_first counts
+ * the messages of the records before i also when n_msgs == 0, and no emsg_out
+ * at or past *n_msgs is written.  *n_won = the EVOTE_WON records (nullable, as
+ * *n_msgs).  removed[] / msgDenied routing (raft.go:376-387) and the deferred
+ * r.Commit copy stay the caller's.
+ * Per record, in Go's order:
+ *   kind 0 (msgHup) runs campaign() first (below).
+ *   The term switch: m.Term == 0 is a local message; m.Term > r.Term runs
+ *     becomeFollower(m.Term, lead) with lead = None for a msgVote and m.From
+ *     for a msgVoteResp (Go's quirk, kept) and sets flags bit 0; m.Term <
+ *     r.Term is EVOTE_IGNORED and nothing else happens.
+ *   Then the case of the state the group is in NOW.
+ * reset(term) writes Term = term, lead = vote = elapsed = 0, voted = granted =
+ *   0, for every peer slot match = 0 and next = lastIndex() + 1 (lastIndex =
+ *   nlog - 1 + log_offset), match = lastIndex() for the slot whose peer_id ==
+ *   id (if any), and pending_conf = 0.  becomeFollower then sets lead and
+ *   state = 0.
+ * msgVote at a follower: Go's short circuit is kept -- isUpToDate is evaluated
+ *   only when vote == 0 or vote == from.  It dereferences at(lastIndex()):
+ *   where that is nil (an empty log at a non-zero offset, or nlog - 1 +
+ *   log_offset wrapped) the status is EWAL_PANIC_NIL_ENTRY; an empty log at
+ *   offset 0 passes isOutOfBounds and indexes past ents: EWAL_PANIC_BOUNDS.
+ *   Granted when log_term > the last entry's term, or equal with index >=
+ *   lastIndex(): elapsed = 0, vote = from, one emsg_out {type 6, to = from,
+ *   from = id, term = r.Term}, EVOTE_GRANTED.  Otherwise the same message with
+ *   reject = 1, EVOTE_REJECTED.  A candidate or a leader (at an equal term, or
+ *   for a local message) always rejects.
+ * msgHup: at a leader EWAL_PANIC_LEADER_TO_CANDIDATE (checked first).  A group
+ *   whose id is not among its first n_peers peer_id gets
+ *   EWAL_UNSUPPORTED_ENCODING: it is not promotable (tickElection never sends
+ *   the message) and its self vote has no slot -- reported, never guessed.
+ *   Otherwise becomeCandidate: reset(Term + 1), vote = id, state = 1; then
+ *   poll(id, true).  With q() = n_peers / 2 + 1 == 1 becomeLeader runs (there is
+ *   nobody to broadcast to): EVOTE_WON.  Otherwise EVOTE_CAMPAIGNED and one
+ *   emsg_out {type 5, to, from = id, term, index = lastIndex(), log_term =
+ *   term(lastIndex())} per peer slot whose peer_id != id, in slot order
+ *   (term() on an empty log at offset 0: EWAL_PANIC_BOUNDS).
+ * msgVoteResp at a candidate: poll(from, !reject) -- only the first answer of
+ *   a from counts; gr = popcount(granted), len(votes) = popcount(voted).  A from
+ *   that is not among the peer slots gets EWAL_UNSUPPORTED_ENCODING (Go would
+ *   count it; the mask cannot).  q() == gr is tested first: becomeLeader, then
+ *   bcastAppend, EVOTE_WON.  Else q() == len(votes) - gr:
+ *   becomeFollower(Term, None), EVOTE_LOST.  Else EVOTE_POLLED.  At a follower
+ *   or a leader: EVOTE_NO_CASE (possibly after the term switch).
+ * becomeLeader: reset(Term), lead = id, state = 2.  Then the scan of
+ *   entries(committed + 1): committed + 1 == log_offset is
+ *   EWAL_PANIC_FIRST_ENTRY; a nil slice is no scan; one entry of d_ents with
+ *   type == 1 (EntryConfChange) sets pending_conf = 1, a second one is
+ *   EWAL_PANIC_DOUBLE_CONF.  Then appendEntry(Entry{}) exactly as
+ *   elead_local_batch_device documents a msgProp: the entry is stored as
+ *   {term, index, 0, 0, type 0, data_nil 1}, the nil-slice case "the log
+ *   becomes the one new entry" included, with unstable = min(unstable, index),
+ *   prs[id].update and maybeCommit (EWAL_PANIC_NIL_PROGRESS when a candidate's
+ *   id is not among its peers).  The winner's bcastAppend is bit for bit
+ *   elead_step_batch_device's sendAppend records, msgSnap included, with its
+ *   panics.
+ * A panicking or unsupported record -- wherever it panics, after a reset or in
+ * the k-th message of a broadcast -- has action EVOTE_PANICKED, emits nothing,
+ * leaves all three records and d_ents exactly as they were before that record,
+ * reports the unchanged term, vote and state with flags 0, and puts the rest
+ * of its group's run at EVOTE_NOT_STEPPED.  Records stepped before it keep
+ * their effect.  The first record of a group with n_peers > 7 gets
+ * EWAL_UNSUPPORTED_ENCODING in the same way.
+ * Written: of a named group term, committed, nlog, match[] and next[]; of its
+ * elead_prop_state unstable and pending_conf; of its evote_state everything
+ * but reserved; becomeLeader's d_ents slots; d_res; d_msgs below *n_msgs.  Only
+ * the words that changed are stored.  Nothing of a group that no record names.
+ * Checked on the device before anything is modified (then the three group
+ * arrays, d_ents, d_res and d_msgs are untouched and the counters are 0):
+ *   EWAL_E_INVAL  group >= G; a group's records not adjacent; kind not 0, 5 or
+ *                 6; reject not 0 or 1; pad or pad2 not 0; and of a named
+ *                 group: evote_state.state > 2; voted or granted with bits at
+ *                 or above min(n_peers, 7); granted & ~voted != 0; a reserved
+ *                 word not 0 in any of its three records; and the group and
+ *                 window checks of elead_local_batch_device
+ *   EWAL_E_NOMEM  a named group has nlog + (the kind-0 and kind-6 records of
+ *                 its run) > ents_cap (the room is decided before any record
+ *                 is stepped); or the messages exceed msgs_cap (INVAL wins
+ *                 when both occur in one call)
+ * and on the host as in elead_local_batch_device, d_pstate and d_vstate
+ * sharing d_groups' rules.  n == 0: EWAL_OK, counters 0.  The entry windows of
+ * the named groups must not overlap each other: the caller's contract. */
+int evote_step_batch_device(ewal_ctx *ctx, elead_group *d_groups, elead_prop_state *d_pstate,
+                            evote_state *d_vstate, uint64_t G, const elead_snap *d_snaps /* G, nullable */,
+                            ewal_entry *d_ents, uint64_t n_ents_total,
+                            const evote_msg *d_in, uint64_t n, evote_result *d_res,
+                            struct emsg_out *d_msgs /* NULL: size query */, uint64_t msgs_cap,
+                            uint64_t *n_msgs, uint64_t *n_won);
+/* For bindings / tests: the sizes of the three records. */
+uint32_t evote_state_size(void);
+uint32_t evote_msg_size(void);
+uint32_t evote_result_size(void);
 
 /* ---- raft ingress: raftpb.Message.Unmarshal, raft/raftpb/raft.pb.go:407-617
  * (called per POST /raft in etcdserver/etcdhttp/http.go:119-146), batched
