@@ -185,6 +185,21 @@ VOTE_FOLLOWER, VOTE_CANDIDATE, VOTE_LEADER = range(3)
 (VOTE_NOT_STEPPED, VOTE_IGNORED, VOTE_GRANTED, VOTE_REJECTED, VOTE_CAMPAIGNED, VOTE_WON, VOTE_LOST, VOTE_POLLED,
  VOTE_NO_CASE, VOTE_PANICKED) = range(10)
 
+class ReadyState(C.Structure):   # eready_state
+    _fields_ = [("hs_term", C.c_uint64), ("hs_vote", C.c_uint64), ("hs_commit", C.c_uint64), ("lead", C.c_uint64),
+                ("state", C.c_uint64), ("snapi", C.c_uint64), ("applied", C.c_uint64), ("soft_dirty", C.c_uint64)]
+
+
+class ReadyResult(C.Structure):   # eready_result
+    _fields_ = [("status", C.c_int32), ("flags", C.c_int32), ("term", C.c_uint64), ("vote", C.c_uint64),
+                ("commit", C.c_uint64), ("ents_first", C.c_uint64), ("n_ents", C.c_uint64),
+                ("committed_first", C.c_uint64), ("n_committed", C.c_uint64), ("save_first", C.c_uint64),
+                ("n_save", C.c_uint64), ("lead", C.c_uint64), ("state", C.c_int32), ("pad", C.c_int32)]
+
+
+# eready_result.flags
+READY_SOFT, READY_HARD, READY_SNAP, READY_UPDATES = 1, 2, 4, 8
+
 SNAP_FIELD_DATA, SNAP_FIELD_UNREC, SNAP_FIELD_NODES, SNAP_FIELD_REMOVED = range(4)
 SEG_UNREC, SEG_ENTRY_UNREC, SEG_ENTRY_DATA, SEG_SNAP_UNREC, SEG_SNAP_DATA, SEG_SNAP_NODE, SEG_SNAP_REMOVED = range(7)
 
@@ -406,6 +421,10 @@ _SIGS = {
     "evote_state_size": (C.c_uint32, []),
     "evote_msg_size": (C.c_uint32, []),
     "evote_result_size": (C.c_uint32, []),
+    "eready_batch_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp,
+                                      C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "eready_state_size": (C.c_uint32, []),
+    "eready_result_size": (C.c_uint32, []),
 }
 for _name, (_res, _args) in _SIGS.items():
     if os.environ.get("EWAL_LIB_PATH") and not hasattr(lib, _name):
@@ -437,7 +456,7 @@ def header_symbols(path=HEADER):
     """Every function declared in include/ewal.h."""
     txt = open(path).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead|vote)_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead|vote|ready)_[a-z0-9_]+)\s*\(", txt)))
 
 
 def status_string(st):

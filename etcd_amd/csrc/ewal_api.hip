@@ -36,6 +36,7 @@
 #include "lead_step.hip"
 #include "lead_prop.hip"
 #include "vote_step.hip"
+#include "ready_step.hip"
 #include "ewal_stage.h"
 #include "ewal_wire.h"
 
@@ -201,6 +202,9 @@ struct ewal_ctx {
   // claims, the terms of the runs' own entries, the runs' message counts,
   // per-workgroup partial sums
   DevBuf lvote;
+  // batched Ready (eready_batch_device): head words, the groups' claims, the
+  // selections' record counts and offsets, per-workgroup partial sums
+  DevBuf lready;
   std::vector<uint64_t> bent_first, bnents;   // per shard: first ent in bents, count
   std::vector<std::vector<ewal_unrec>> bunrec;       // per shard replayed alone: its XXX_unrecognized side list
   std::vector<std::vector<uint8_t>> bunrec_bytes;
@@ -3644,6 +3648,82 @@ int evote_step_batch_device(ewal_ctx *c, elead_group *d_groups, elead_prop_state
   EW_CHECK(hipStreamSynchronize(c->stream));
   if (n_msgs) *n_msgs = h.n_msgs;
   if (n_won) *n_won = h.n_committed;
+  return EWAL_OK;
+}
+
+uint32_t eready_state_size(void) { return sizeof(eready_state); }
+uint32_t eready_result_size(void) { return sizeof(eready_result); }
+
+static_assert(sizeof(eready_state) == 64 && sizeof(eready_result) == 96 && sizeof(ewal_save_rec) == 56 &&
+                  sizeof(ewal_entry) == 40 && sizeof(EreadyRec) == 32 && offsetof(eready_state, applied) == 48 &&
+                  offsetof(eready_result, ents_first) == 32 && offsetof(eready_result, save_first) == 64 &&
+                  offsetof(eready_result, state) == 88 && offsetof(ewal_save_rec, data_nil) == 48,
+              "eready layout");
+int eready_batch_device(ewal_ctx *c, const elead_group *d_groups, elead_prop_state *d_pstate,
+                        const evote_state *d_vstate, eready_state *d_rstate, uint64_t G, const elead_snap *d_snaps,
+                        const ewal_entry *d_ents, uint64_t n_ents_total, const uint64_t *d_sel, uint64_t n,
+                        eready_result *d_res, ewal_save_rec *d_save, uint64_t save_cap, uint64_t *n_save,
+                        uint64_t *n_ready) {
+  if (n_save) *n_save = 0;
+  if (n_ready) *n_ready = 0;
+  if (!c) return EWAL_E_INVAL;
+  if (n >= 0x7fffffffull || G >= 0x7fffffffull) return EWAL_E_INVAL;
+  if (!d_sel && n != G) return EWAL_E_INVAL;
+  if (n == 0) return EWAL_OK;
+  if (!d_groups || !d_pstate || !d_vstate || !d_rstate || !d_res || (n_ents_total && !d_ents)) return EWAL_E_INVAL;
+  if ((((uintptr_t)d_groups | (uintptr_t)d_pstate | (uintptr_t)d_vstate | (uintptr_t)d_rstate | (uintptr_t)d_snaps |
+        (uintptr_t)d_res | (uintptr_t)d_save) &
+       15) != 0 ||
+      (((uintptr_t)d_ents | (uintptr_t)d_sel) & 7) != 0)
+    return EWAL_E_INVAL;
+  EW_CHECK(hipSetDevice(c->device));
+  forget_records(c);
+  // scratch: head | claim[G] | rec[n] | partial[2 * workgroups]
+  const uint32_t blocks = grid_for(n, 256);
+  const size_t o_claim = 64, o_rec = (o_claim + (d_sel ? (size_t)G * 4 : 0) + 15) & ~(size_t)15,
+               o_part = o_rec + (size_t)n * sizeof(EreadyRec);
+  EW_CHECK(c->lready.ensure(o_part + (size_t)blocks * 16));
+  uint8_t *base = c->lready.as<uint8_t>();
+  EreadyArgs a{};
+  a.groups = d_groups;
+  a.pstate = d_pstate;
+  a.vstate = d_vstate;
+  a.rstate = d_rstate;
+  a.G = G;
+  a.snaps = d_snaps;
+  a.ents = d_ents;
+  a.n_ents_total = n_ents_total;
+  a.sel = d_sel;
+  a.n = n;
+  a.res = d_res;
+  a.save = d_save;
+  a.blocks = blocks;
+  a.head = (EleadHead *)base;
+  a.claim = (uint32_t *)(base + o_claim);
+  a.rec = (EreadyRec *)(base + o_rec);
+  a.partial = (unsigned long long *)(base + o_part);
+  EW_CHECK(hipEventRecord(c->ev0, c->stream));
+  EW_CHECK(hipMemsetAsync(a.head, 0, sizeof(EleadHead), c->stream));
+  if (d_sel && G) EW_CHECK(hipMemsetAsync(a.claim, 0xff, (size_t)G * 4, c->stream));
+  hipLaunchKernelGGL(k_ready_count, dim3(blocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.partial, blocks, a.head);
+  EW_CHECK(hipGetLastError());
+  // the one decision point: nothing of the caller's has been modified yet
+  EleadHead h;
+  EW_CHECK(hipMemcpyAsync(&h, a.head, sizeof(EleadHead), hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  if (h.errflag & EREADY_ERR_INVAL) return EWAL_E_INVAL;
+  if (d_save && h.n_msgs > save_cap) return EWAL_E_NOMEM;
+  a.n_save = h.n_msgs;
+  if (d_save)
+    hipLaunchKernelGGL(k_ready_emit<true>, dim3(std::max(blocks, grid_for(a.n_save, 256))), dim3(256), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(k_ready_emit<false>, dim3(blocks), dim3(256), 0, c->stream, a);
+  EW_CHECK(hipGetLastError());
+  EW_CHECK(hipEventRecord(c->ev1, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  if (n_save) *n_save = h.n_msgs;
+  if (n_ready) *n_ready = h.n_committed;
   return EWAL_OK;
 }
 

@@ -75,6 +75,23 @@ EWAL_HD inline int32_t log_term(const State &s, uint64_t i, const TermAt &term_a
   return ST_OK;
 }
 
+// raftLog.slice(lo, hi) (raft/log.go:202-210) of a log of nlog entries at
+// offset off, as positions in ents: [*first, *first + *n), *n == 0 where Go
+// returns nil; ST_PANIC_BOUNDS where Go indexes past ents (only a wrapped
+// lastIndex() gets there).
+EWAL_HD inline int32_t log_slice(uint64_t off, uint64_t nlog, uint64_t lo, uint64_t hi, uint64_t *first, uint64_t *n) {
+  const uint64_t last = nlog - 1 + off;              // lastIndex(), uint64 wrap
+  *first = 0;
+  *n = 0;
+  if (lo >= hi) return ST_OK;
+  if (lo < off || lo > last || hi - 1 < off || hi - 1 > last) return ST_OK;   // isOutOfBounds(lo) || isOutOfBounds(hi - 1)
+  const uint64_t lo_p = lo - off, hi_p = hi - off;
+  if (lo_p > hi_p || hi_p > nlog) return ST_PANIC_BOUNDS;
+  *first = lo_p;
+  *n = hi_p - lo_p;
+  return ST_OK;
+}
+
 // sendAppend for a peer whose Progress.next is `next`: the message, or the
 // class of Go's panic.  LOAD false: the class alone, no term is read.
 template <bool LOAD, class TermAt>
@@ -95,15 +112,7 @@ EWAL_HD inline int32_t send_append(const State &s, uint64_t to, uint64_t next, c
   const int32_t st = log_term<LOAD>(s, index, term_at, &m->log_term);
   if (st != ST_OK) return st;
   if (next == s.off) return ST_PANIC_FIRST_ENTRY;    // entries(i) with i == offset
-  // slice(next, lastIndex() + 1)
-  const uint64_t last = s.nlog - 1 + s.off, hi = last + 1;
-  if (next >= hi) return ST_OK;                      // nil
-  if (next < s.off || next > last) return ST_OK;     // isOutOfBounds(lo); that of hi - 1 makes this one true
-  const uint64_t lo_p = next - s.off, hi_p = hi - s.off;
-  if (lo_p > hi_p || hi_p > s.nlog) return ST_PANIC_BOUNDS;
-  m->efirst = lo_p;
-  m->nents = hi_p - lo_p;
-  return ST_OK;
+  return log_slice(s.off, s.nlog, next, s.nlog - 1 + s.off + 1, &m->efirst, &m->nents);   // slice(next, lastIndex() + 1)
 }
 
 EWAL_HD inline uint64_t n_slots(const State &s) { return s.np < PEERS ? s.np : PEERS; }

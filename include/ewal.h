@@ -1198,6 +1198,127 @@ uint32_t evote_state_size(void);
 uint32_t evote_msg_size(void);
 uint32_t evote_result_size(void);
 
+/* ---- Ready: newReady (raft/node.go:332-348), node.run's accept branch
+ * (:239-255) and Storage.Save's record order (wal/wal.go:281-288, called
+ * before any message is sent, etcdserver/server.go:256-259).  Batched over n
+ * selected groups of G -- the joint between the step calls above and the write
+ * side: what the steps left in elead_group, elead_prop_state and evote_state
+ * comes in; per group a Ready (the HardState, the unstable entries and the
+ * newly committed entries as views of d_ents, the SoftState, whether a
+ * snapshot appeared) and the ewal_save_rec records that ewal_save_device takes
+ * directly come out, and the group is advanced as the accept branch does.  The
+ * three step records are unchanged (the same arrays feed every call); what
+ * node.run keeps in locals and raftLog.applied live in the side record below.
+ * All arithmetic is Go's uint64 and wraps; lastIndex = nlog - 1 + log_offset. */
+typedef struct eready_state {       /* 64 bytes; a DEVICE array of G, updated in place */
+  uint64_t hs_term, hs_vote, hs_commit;  /* prevHardSt (node.go:196, 243-245) */
+  uint64_t lead, state;             /* prevSoftSt.Lead / .RaftState (node.go:195, 240-242) */
+  uint64_t snapi;                   /* prevSnapi (node.go:197, 246-248) */
+  uint64_t applied;                 /* raftLog.applied (log.go:17, 109-113) */
+  uint64_t soft_dirty;              /* 0 or 1, see below */
+} eready_state;
+#define EREADY_SOFT 1
+#define EREADY_HARD 2
+#define EREADY_SNAP 4
+#define EREADY_UPDATES 8
+typedef struct eready_result {      /* 96 bytes; a DEVICE array of n */
+  int32_t status;                   /* EWAL_OK, EWAL_PANIC_BOUNDS, EWAL_UNSUPPORTED_ENCODING */
+  int32_t flags;                    /* EREADY_SOFT=1, EREADY_HARD=2, EREADY_SNAP=4, EREADY_UPDATES=8 */
+  uint64_t term, vote, commit;      /* rd.HardState: all 0 when there is no update */
+  uint64_t ents_first, n_ents;      /* rd.Entries as a view of d_ents; nil is 0, 0 */
+  uint64_t committed_first, n_committed;   /* rd.CommittedEntries, likewise */
+  uint64_t save_first, n_save;      /* this group's records in d_save */
+  uint64_t lead;                    /* rd.SoftState (valid when EREADY_SOFT, else 0) */
+  int32_t state, pad;
+} eready_result;
+/* Selection i is group d_sel[i], or group i when d_sel == NULL (then n == G).
+ * Per selected group, in Go's order:
+ *   rd.Entries = unstableEnts() = slice(unstable, lastIndex + 1) (raft/log.go:
+ *     86-94, 202-210): nil when lo >= hi (lastIndex + 1 wrapping to 0 included)
+ *     or isOutOfBounds holds for either end; otherwise the view ents_first +
+ *     (unstable - log_offset), n_ents = lastIndex + 1 - unstable.
+ *   rd.CommittedEntries = nextEnts() (log.go:102-107): nil unless committed >
+ *     applied, then slice(applied + 1, committed + 1) with the same nil rules.
+ *   A slice that passes both isOutOfBounds tests but indexes past ents (only a
+ *     wrapped nlog - 1 + log_offset gets there) is EWAL_PANIC_BOUNDS.
+ *   rd.HardState: r.HardState is {group.term, vstate.vote, group.committed} --
+ *     every Step ends with r.Commit = raftLog.committed (raft/raft.go:374), the
+ *     copy the step calls leave to the caller: it lands here.  StartNode's
+ *     window before the first Step (node.go:141-142 set committed without it)
+ *     is the caller's: it seeds hs_* from the HardState it restored, not from
+ *     the log.  rd.HardState is that triple when it differs from hs_*, else
+ *     zero; EREADY_HARD iff it is not the empty state.  Go's quirk is kept: a
+ *     differing but all-zero HardState looks like "no update" and is never
+ *     accepted (node.go:243).
+ *   rd.SoftState (EREADY_SOFT): vstate.lead != lead, vstate.state != state, or
+ *     soft_dirty == 1.  SoftState.Nodes and ShouldStop change only through
+ *     addNode / removeNode / msgDenied, the caller's on the host: after any of
+ *     them it sets soft_dirty.  Go compares Nodes with reflect.DeepEqual over a
+ *     slice built in map order, so with two or more peers Go's own answer is
+ *     not deterministic; that is NOT reproduced -- the library's order is slot
+ *     order, as everywhere else.
+ *   rd.Snapshot: raftLog.snapshot.Index is d_snaps[g].index (0 when d_snaps ==
+ *     NULL); EREADY_SNAP iff it differs from snapi and is not 0.  The snapshot
+ *     is d_snaps[g]; saving it is esnap_save_*'s job and the caller's.
+ *   EREADY_UPDATES = containsUpdates() without its Messages term (node.go:
+ *     83-86): the messages are the step calls' emsg_out output, the caller
+ *     knows their count, and accepting a group that has only messages changes
+ *     nothing.
+ * Storage.Save(rd.HardState, rd.Entries) as ewal_save_rec records, per group:
+ *   one EWAL_SAVE_STATE {a = term, b = vote, c = commit} iff EREADY_HARD
+ *   (SaveState skips the empty state), then one EWAL_SAVE_ENTRY per entry of
+ *   rd.Entries in order {etype = type, a = term, b = index, c = 0, data_off,
+ *   data_len and data_nil copied, pad 0}.  The dummy entry at position 0 is
+ *   saved when unstable == 0, as Go does.  The records are dense, ordered by
+ *   selection position, then as above; save_first counts the records of the
+ *   selections before it also when n_save == 0; nothing at or past *n_save is
+ *   written.  One ewal_save_device call is one CRC chain: the groups'
+ *   [save_first, + n_save) ranges are how a caller with one WAL per group cuts
+ *   d_save.  An unstable entry with data_nil == 2 has its bytes outside d_data:
+ *   the group gets EWAL_UNSUPPORTED_ENCODING -- reported, never guessed.
+ * Accept (only when d_save != NULL, only groups with status EWAL_OK):
+ *   EREADY_SOFT: lead / state overwritten, soft_dirty = 0; EREADY_HARD: hs_*
+ *   overwritten; EREADY_SNAP: snapi = index; resetNextEnts: applied =
+ *   committed when committed > applied (also when the slice came out nil --
+ *   Go's quirk); resetUnstable: elead_prop_state.unstable = lastIndex + 1.
+ *   Only the words that changed are stored.
+ * Written: d_rstate and elead_prop_state.unstable of accepted groups, d_res,
+ * d_save below *n_save.  elead_group, evote_state, d_snaps and d_ents are
+ * never written; groups not selected are not touched.  A panicking or
+ * unsupported group has flags 0, every other result field but status and
+ * save_first 0, no save records, and is left exactly as it was.
+ * d_save == NULL is the peek and the size query: d_res, *n_save and *n_ready
+ * are filled and nothing else is modified.  *n_ready = the groups with
+ * EREADY_UPDATES (both counters nullable).
+ * Not covered: entries that elog_append_batch_device appended into its own
+ * d_terms windows (a follower's log lives in another layout), and one chained
+ * save per group's own WAL (see save_first above).
+ * Checked on the device before anything is modified (then every array is
+ * untouched and the counters are 0):
+ *   EWAL_E_INVAL  a selected group >= G; a group selected twice; state > 2 in
+ *                 the evote_state or the eready_state; soft_dirty > 1;
+ *                 elead_group.reserved, elead_prop_state.reserved or
+ *                 evote_state.reserved not 0; ents_first + nlog outside
+ *                 n_ents_total or wrapping
+ *   EWAL_E_NOMEM  the save records exceed save_cap (INVAL wins when both occur)
+ * and on the host: NULL arguments, d_groups / d_pstate / d_vstate / d_rstate /
+ * d_snaps / d_res / d_save not 16-byte aligned, d_ents or d_sel not 8-byte
+ * aligned, n or G >= 2^31 - 1, d_sel == NULL with n != G: EWAL_E_INVAL.  n ==
+ * 0: EWAL_OK, counters 0.  A compute call on the ctx's stream;
+ * ewal_last_device_ms covers it; a repeated call of the same or a smaller
+ * shape allocates nothing. */
+int eready_batch_device(ewal_ctx *ctx, const elead_group *d_groups, elead_prop_state *d_pstate,
+                        const evote_state *d_vstate, eready_state *d_rstate, uint64_t G,
+                        const elead_snap *d_snaps /* G, nullable */,
+                        const ewal_entry *d_ents, uint64_t n_ents_total,
+                        const uint64_t *d_sel /* n group numbers; NULL: n == G, group i */, uint64_t n,
+                        eready_result *d_res,
+                        ewal_save_rec *d_save /* NULL: peek */, uint64_t save_cap,
+                        uint64_t *n_save, uint64_t *n_ready);
+/* For bindings / tests: the sizes of the two records. */
+uint32_t eready_state_size(void);
+uint32_t eready_result_size(void);
+
 /* ---- raft ingress: raftpb.Message.Unmarshal, raft/raftpb/raft.pb.go:407-617
  * (called per POST /raft in etcdserver/etcdhttp/http.go:119-146), batched
  * over n messages resident in one device buffer at offs[i], lens[i] (host
