@@ -200,6 +200,25 @@ class ReadyResult(C.Structure):   # eready_result
 # eready_result.flags
 READY_SOFT, READY_HARD, READY_SNAP, READY_UPDATES = 1, 2, 4, 8
 
+
+class FollowMsg(C.Structure):   # efollow_msg
+    _fields_ = [("group", C.c_uint64), ("kind", C.c_uint64), ("from_", C.c_uint64), ("term", C.c_uint64),
+                ("index", C.c_uint64), ("log_term", C.c_uint64), ("commit", C.c_uint64), ("ents_first", C.c_uint64),
+                ("n_ents", C.c_uint64), ("data_delta", C.c_uint64), ("snap", C.c_uint64), ("pad", C.c_uint64)]
+
+
+class FollowResult(C.Structure):   # efollow_result
+    _fields_ = [("status", C.c_int32), ("action", C.c_int32), ("msg_first", C.c_uint64), ("n_msgs", C.c_uint64),
+                ("conflict", C.c_uint64), ("app_first", C.c_uint64), ("n_app", C.c_uint64), ("dst_first", C.c_uint64),
+                ("last_index", C.c_uint64), ("committed", C.c_uint64), ("term", C.c_uint64), ("state", C.c_int32),
+                ("flags", C.c_int32), ("pad", C.c_uint64)]
+
+
+# efollow_msg.kind, efollow_result.action
+FOLLOW_MSG_APP, FOLLOW_MSG_SNAP = 3, 7
+(FOLLOW_NOT_STEPPED, FOLLOW_IGNORED, FOLLOW_NO_CASE, FOLLOW_APPENDED, FOLLOW_REJECTED, FOLLOW_RESTORED,
+ FOLLOW_SNAP_STALE, FOLLOW_DEFERRED, FOLLOW_PANICKED) = range(9)
+
 SNAP_FIELD_DATA, SNAP_FIELD_UNREC, SNAP_FIELD_NODES, SNAP_FIELD_REMOVED = range(4)
 SEG_UNREC, SEG_ENTRY_UNREC, SEG_ENTRY_DATA, SEG_SNAP_UNREC, SEG_SNAP_DATA, SEG_SNAP_NODE, SEG_SNAP_REMOVED = range(7)
 
@@ -425,6 +444,11 @@ _SIGS = {
                                       C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "eready_state_size": (C.c_uint32, []),
     "eready_result_size": (C.c_uint32, []),
+    "efollow_step_batch_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp,
+                                            C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64,
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "efollow_msg_size": (C.c_uint32, []),
+    "efollow_result_size": (C.c_uint32, []),
 }
 for _name, (_res, _args) in _SIGS.items():
     if os.environ.get("EWAL_LIB_PATH") and not hasattr(lib, _name):
@@ -456,7 +480,7 @@ def header_symbols(path=HEADER):
     """Every function declared in include/ewal.h."""
     txt = open(path).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead|vote|ready)_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead|vote|ready|follow)_[a-z0-9_]+)\s*\(", txt)))
 
 
 def status_string(st):

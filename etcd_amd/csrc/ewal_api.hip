@@ -37,6 +37,7 @@
 #include "lead_prop.hip"
 #include "vote_step.hip"
 #include "ready_step.hip"
+#include "follow_step.hip"
 #include "ewal_stage.h"
 #include "ewal_wire.h"
 
@@ -205,6 +206,10 @@ struct ewal_ctx {
   // batched Ready (eready_batch_device): head words, the groups' claims, the
   // selections' record counts and offsets, per-workgroup partial sums
   DevBuf lready;
+  // batched follower step (efollow_step_batch_device): two head words, the
+  // groups' claims, the runs' message counts and copy descriptors,
+  // per-workgroup partial sums of both
+  DevBuf lfollow;
   std::vector<uint64_t> bent_first, bnents;   // per shard: first ent in bents, count
   std::vector<std::vector<ewal_unrec>> bunrec;       // per shard replayed alone: its XXX_unrecognized side list
   std::vector<std::vector<uint8_t>> bunrec_bytes;
@@ -3724,6 +3729,107 @@ int eready_batch_device(ewal_ctx *c, const elead_group *d_groups, elead_prop_sta
   EW_CHECK(hipStreamSynchronize(c->stream));
   if (n_save) *n_save = h.n_msgs;
   if (n_ready) *n_ready = h.n_committed;
+  return EWAL_OK;
+}
+
+uint32_t efollow_msg_size(void) { return sizeof(efollow_msg); }
+uint32_t efollow_result_size(void) { return sizeof(efollow_result); }
+
+static_assert(sizeof(efollow_msg) == 96 && sizeof(efollow_result) == 96 && sizeof(EfollowCopy) == 48 &&
+                  offsetof(efollow_msg, ents_first) == 56 && offsetof(efollow_msg, snap) == 80 &&
+                  offsetof(efollow_result, conflict) == 24 && offsetof(efollow_result, dst_first) == 48 &&
+                  offsetof(efollow_result, state) == 80 && offsetof(eready_state, applied) == 48 &&
+                  offsetof(elead_snap, nodes_off) == 32,
+              "efollow layout");
+int efollow_step_batch_device(ewal_ctx *c, elead_group *d_groups, elead_prop_state *d_pstate, evote_state *d_vstate,
+                              eready_state *d_rstate, uint64_t G, elead_snap *d_snaps, ewal_entry *d_ents,
+                              uint64_t n_ents_total, const ewal_entry *d_src, uint64_t n_src_total,
+                              const elead_snap *d_in_snaps, uint64_t n_in_snaps, const uint64_t *d_u64, uint64_t n_u64,
+                              const efollow_msg *d_in, uint64_t n, efollow_result *d_res, emsg_out *d_msgs,
+                              uint64_t msgs_cap, uint64_t *n_msgs, uint64_t *n_appended, uint64_t *n_restored) {
+  if (n_msgs) *n_msgs = 0;
+  if (n_appended) *n_appended = 0;
+  if (n_restored) *n_restored = 0;
+  if (!c) return EWAL_E_INVAL;
+  if (n >= 0x7fffffffull || G >= 0x7fffffffull) return EWAL_E_INVAL;
+  if (n == 0) return EWAL_OK;
+  if (!d_groups || !d_pstate || !d_vstate || !d_in || !d_res || (n_ents_total && !d_ents) || (n_src_total && !d_src) ||
+      (n_in_snaps && !d_in_snaps) || (n_u64 && !d_u64))
+    return EWAL_E_INVAL;
+  if ((((uintptr_t)d_groups | (uintptr_t)d_pstate | (uintptr_t)d_vstate | (uintptr_t)d_rstate | (uintptr_t)d_snaps |
+        (uintptr_t)d_in_snaps | (uintptr_t)d_in | (uintptr_t)d_res | (uintptr_t)d_msgs) &
+       15) != 0 ||
+      (((uintptr_t)d_ents | (uintptr_t)d_src | (uintptr_t)d_u64) & 7) != 0)
+    return EWAL_E_INVAL;
+  EW_CHECK(hipSetDevice(c->device));
+  forget_records(c);
+  // scratch: head | copy head | claim[G] | run_msgs[n] | cp[n] | partial[2 * workgroups] | cpart[2 * workgroups]
+  const uint32_t blocks = grid_for(n, 256);
+  const size_t o_chead = 64, o_claim = 128, o_run = (o_claim + (size_t)G * 4 + 15) & ~(size_t)15,
+               o_cp = (o_run + (size_t)n * 8 + 15) & ~(size_t)15, o_part = o_cp + (size_t)n * sizeof(EfollowCopy),
+               o_cpart = o_part + (size_t)blocks * 16;
+  EW_CHECK(c->lfollow.ensure(o_cpart + (size_t)blocks * 16));
+  uint8_t *base = c->lfollow.as<uint8_t>();
+  EfollowArgs a{};
+  a.p.groups = d_groups;
+  a.p.state = d_pstate;
+  a.p.G = G;
+  a.p.snaps = d_snaps;
+  a.p.ents = d_ents;
+  a.p.n_ents_total = n_ents_total;
+  a.p.n = n;
+  a.p.msgs = d_msgs;
+  a.p.head = (EleadHead *)base;
+  a.p.claim = (uint32_t *)(base + o_claim);
+  a.p.partial = (unsigned long long *)(base + o_part);
+  a.vstate = d_vstate;
+  a.rstate = d_rstate;
+  a.snaps = d_snaps;
+  a.src = d_src;
+  a.n_src_total = n_src_total;
+  a.in_snaps = d_in_snaps;
+  a.n_in_snaps = n_in_snaps;
+  a.u64 = d_u64;
+  a.n_u64 = n_u64;
+  a.in = d_in;
+  a.n = n;
+  a.res = d_res;
+  a.run_msgs = (unsigned long long *)(base + o_run);
+  a.cp = (EfollowCopy *)(base + o_cp);
+  a.cpart = (unsigned long long *)(base + o_cpart);
+  a.chead = (EleadHead *)(base + o_chead);
+  a.blocks = blocks;
+  EW_CHECK(hipEventRecord(c->ev0, c->stream));
+  EW_CHECK(hipMemsetAsync(base, 0, 128, c->stream));
+  if (G) EW_CHECK(hipMemsetAsync(a.p.claim, 0xff, (size_t)G * 4, c->stream));
+  hipLaunchKernelGGL(k_follow_count, dim3(blocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.p.partial, blocks, a.p.head);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.cpart, blocks, a.chead);
+  EW_CHECK(hipGetLastError());
+  // the one decision point: nothing of the caller's has been modified yet
+  static_assert(sizeof(EleadHead) <= 64, "the two head words' slots");
+  uint8_t hb[128];
+  EW_CHECK(hipMemcpyAsync(hb, base, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  EleadHead h[2];
+  std::memcpy(&h[0], hb, sizeof(EleadHead));
+  std::memcpy(&h[1], hb + o_chead, sizeof(EleadHead));
+  if (h[0].errflag & EFOLLOW_ERR_INVAL) return EWAL_E_INVAL;
+  if (h[0].errflag & EFOLLOW_ERR_NOMEM) return EWAL_E_NOMEM;
+  if (d_msgs && h[0].n_msgs > msgs_cap) return EWAL_E_NOMEM;
+  a.n_copy = h[1].n_msgs;
+  if (d_msgs) {
+    hipLaunchKernelGGL(k_follow_apply<true>, dim3(blocks), dim3(256), 0, c->stream, a);
+    if (a.n_copy) hipLaunchKernelGGL(k_follow_copy, dim3(grid_for(a.n_copy, 256)), dim3(256), 0, c->stream, a);
+  } else {
+    hipLaunchKernelGGL(k_follow_apply<false>, dim3(blocks), dim3(256), 0, c->stream, a);
+  }
+  EW_CHECK(hipGetLastError());
+  EW_CHECK(hipEventRecord(c->ev1, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  if (n_msgs) *n_msgs = h[0].n_msgs;
+  if (n_appended) *n_appended = h[1].n_msgs;
+  if (n_restored) *n_restored = h[0].n_committed;
   return EWAL_OK;
 }
 

@@ -1291,8 +1291,9 @@ typedef struct eready_result {      /* 96 bytes; a DEVICE array of n */
  * are filled and nothing else is modified.  *n_ready = the groups with
  * EREADY_UPDATES (both counters nullable).
  * Not covered: entries that elog_append_batch_device appended into its own
- * d_terms windows (a follower's log lives in another layout), and one chained
- * save per group's own WAL (see save_first above).
+ * d_terms windows (that call keeps terms only; a follower stepped by
+ * efollow_step_batch_device, below, has its entries in d_ents and is covered),
+ * and one chained save per group's own WAL (see save_first above).
  * Checked on the device before anything is modified (then every array is
  * untouched and the counters are 0):
  *   EWAL_E_INVAL  a selected group >= G; a group selected twice; state > 2 in
@@ -1318,6 +1319,155 @@ int eready_batch_device(ewal_ctx *ctx, const elead_group *d_groups, elead_prop_s
 /* For bindings / tests: the sizes of the two records. */
 uint32_t eready_state_size(void);
 uint32_t eready_result_size(void);
+
+/* ---- follower step: raft.Step for msgApp and msgSnap, raft/raft.go:372-408.
+ * Batched over n messages for G raft groups -- the other N - 1 replicas' half
+ * of a replication round, on the records the calls above share: Step's term
+ * switch (:393-405), the msgApp and msgSnap cases of stepFollower (:504-510)
+ * and stepCandidate (:476-481; stepLeader has none), handleAppendEntries
+ * (:410-416), handleSnapshot (:418-424), raft.restore (:535-554) and, from
+ * raft/log.go, maybeAppend, findConflict, append, matchTerm, at, slice,
+ * isOutOfBounds, lastIndex and restore.  A group is its elead_group, its
+ * elead_prop_state, its evote_state and (for a restore) its eready_state and
+ * d_snaps[g]; its log is the window d_ents[ents_first, + ents_cap).  What the
+ * leader-side calls emit as msgApp / msgSnap comes in; the grown or restored
+ * log -- whole 40-byte entries, so eready_batch_device and ewal_save_device
+ * take a follower as they take a leader -- and one msgAppResp per stepped
+ * message, as emsg_out records that elead_step_batch_device's caller unpacks
+ * or emsg_encode_batch_device marshals, come out.  All arithmetic is Go's
+ * uint64 and wraps; lastIndex = nlog - 1 + log_offset. */
+typedef struct efollow_msg {        /* 96 bytes; one message; a DEVICE array of n */
+  uint64_t group;                   /* which group steps it */
+  uint64_t kind;                    /* 3 = msgApp, 7 = msgSnap (raft.go:17-34) */
+  uint64_t from, term, index, log_term, commit;   /* m.From, m.Term, m.Index, m.LogTerm, m.Commit */
+  uint64_t ents_first, n_ents;      /* m.Entries = d_src[ents_first, + n_ents) (ewal_entry) */
+  uint64_t data_delta;              /* added, wrapping, to data_off of every copied entry whose data_nil == 0:
+                                       it rebases an ingress buffer into d_data */
+  uint64_t snap;                    /* kind 7: m.Snapshot is d_in_snaps[snap] */
+  uint64_t pad;                     /* 0 */
+} efollow_msg;
+enum { EFOLLOW_NOT_STEPPED = 0,     /* after a panic in its group's run: the caller's to step */
+       EFOLLOW_IGNORED = 1,         /* 0 < m.Term < r.Term */
+       EFOLLOW_NO_CASE = 2,         /* a leader (at an equal term, or for a local message): no case, no message */
+       EFOLLOW_APPENDED = 3,        /* maybeAppend returned true, also with n_app == 0 */
+       EFOLLOW_REJECTED = 4,        /* matchTerm failed: the response rejects */
+       EFOLLOW_RESTORED = 5,        /* msgSnap: raft.restore returned true */
+       EFOLLOW_SNAP_STALE = 6,      /* msgSnap: s.Index <= committed, restore returned false */
+       EFOLLOW_DEFERRED = 7,        /* the run rule below: the caller's to step in the next call */
+       EFOLLOW_PANICKED = 8 };      /* Go panics (status says where), or the record is unsupported */
+typedef struct efollow_result {     /* 96 bytes; a DEVICE array of n */
+  int32_t status, action;           /* EWAL_OK, an EWAL_PANIC_ class, EWAL_UNSUPPORTED_ENCODING; EFOLLOW_* */
+  uint64_t msg_first, n_msgs;       /* its response: d_msgs[msg_first, + n_msgs), n_msgs 0 or 1 */
+  uint64_t conflict;                /* findConflict's ci; 0: none */
+  uint64_t app_first, n_app;        /* the entries appended: d_src[app_first, + n_app), a suffix of the
+                                       message's range; 0, 0: nothing appended */
+  uint64_t dst_first;               /* where they went: d_ents[dst_first, + n_app); 0 when n_app == 0 */
+  uint64_t last_index, committed, term;   /* lastIndex(), raftLog.committed, raft.Term after this record */
+  int32_t state;                    /* raft.state after this record */
+  int32_t flags;                    /* bit 0: Step's term switch ran becomeFollower; bit 1: a candidate conceded */
+  uint64_t pad;
+} efollow_result;
+/* Order, output placement, the size query (d_msgs == NULL), the stream, the
+ * timing and the allocation rule are evote_step_batch_device's: a group's
+ * records are adjacent and stepped in array order, each one seeing what the
+ * previous one left, the responses are dense and ordered by record, msg_first
+ * counts the responses of the records before i also when n_msgs == 0, and no
+ * emsg_out at or past *n_msgs is written.  removed[] / msgDenied routing and
+ * the deferred r.Commit copy stay the caller's.
+ * The run rule.  After a record of a run has appended entries (n_app > 0) or
+ * restored, a later record of that run that carries entries (n_ents > 0) or is
+ * a msgSnap is EFOLLOW_DEFERRED with status EWAL_OK, and so is the rest of the
+ * run: no effect, no message, the caller's to step in the next call.  Records
+ * without entries (heartbeats, commit-only msgApp) are stepped and see the
+ * grown or restored log.
+ * Per record, in Go's order:
+ *   The term switch: m.Term == 0 is a local message; m.Term > r.Term runs
+ *     becomeFollower(m.Term, m.From) -- reset as evote_step_batch_device
+ *     documents it -- and sets flags bit 0; m.Term < r.Term is EFOLLOW_IGNORED.
+ *   Then the case of the state the group is in NOW.
+ *     follower, msgApp: elapsed = 0, lead = from, handleAppendEntries.
+ *     follower, msgSnap: elapsed = 0, handleSnapshot; lead is NOT set (Go's
+ *       quirk, kept).
+ *     candidate, msgApp: becomeFollower(r.Term, from), flags bit 1, then
+ *       handleAppendEntries.
+ *     candidate, msgSnap: becomeFollower(m.Term, from), flags bit 1, then
+ *       handleSnapshot; with m.Term == 0 this sets Term to 0 (Go's quirk, kept).
+ *     leader: EFOLLOW_NO_CASE.
+ *   handleAppendEntries: maybeAppend exactly as elog_append_batch_device
+ *     documents it (matchTerm, findConflict by position,
+ *     EWAL_PANIC_COMMITTED_CONFLICT, EWAL_PANIC_BOUNDS, committed =
+ *     max(committed, min(commit, index + n_ents))), on the terms of d_ents.
+ *     With ci > 0 the whole entries d_src[app_first + j] are copied to
+ *     d_ents[ents_first + (ci - log_offset) + j], j < n_app, data_off rebased
+ *     by data_delta where data_nil == 0 (an entry with data_nil == 2 is copied
+ *     untouched: Ready reports it); nlog = ci - log_offset + n_app;
+ *     elead_prop_state.unstable = min(unstable, ci).  One emsg_out {type 4, to
+ *     = from, from = id, term = r.Term, index = lastIndex()}: EFOLLOW_APPENDED
+ *     -- or index = m.Index with reject = 1: EFOLLOW_REJECTED.
+ *   handleSnapshot, s = d_in_snaps[snap]: s.index <= committed is
+ *     EFOLLOW_SNAP_STALE, the response carries index = committed.  Otherwise
+ *     EFOLLOW_RESTORED: d_ents[ents_first] = {term: s.term, index 0, data 0/0,
+ *     type 0, data_nil 1}, nlog = 1, log_offset = committed = s.index,
+ *     unstable = s.index + 1, eready_state.applied = s.index, d_snaps[g] = s;
+ *     prs is rebuilt from s.Nodes = d_u64[nodes_off, + n_nodes): the distinct
+ *     ids take the slots in first-occurrence order, the slot whose id equals id
+ *     gets (match, next) = (s.index, s.index + 1), the others (0, s.index + 1),
+ *     the slots past them are zeroed; eready_state.soft_dirty = 1 iff n_peers
+ *     or one of the first n_peers peer_id changed; pending_conf and the votes
+ *     are untouched; the response carries index = lastIndex() = s.index.
+ *     r.removed from RemovedNodes stays the caller's, as removed[] does
+ *     everywhere: EFOLLOW_RESTORED tells it.
+ * EWAL_UNSUPPORTED_ENCODING, reported, never guessed: the first record of a
+ * group with n_peers > 7; a restore with n_nodes > 64 or more than 7 distinct
+ * ids; a restore while evote_state.voted != 0 (unreachable in Go: every way of
+ * becoming a follower resets the votes).
+ * A panicking or unsupported record has action EFOLLOW_PANICKED, emits
+ * nothing, leaves all four records, d_snaps and d_ents exactly as they were
+ * before that record, reports the unchanged last_index, committed, term and
+ * state with flags 0, and puts the rest of its run at EFOLLOW_NOT_STEPPED.
+ * Records stepped before it keep their effect.
+ * Written: of a named group term, committed, log_offset, nlog, n_peers,
+ * peer_id[], match[] and next[]; of its elead_prop_state unstable and
+ * pending_conf; of its evote_state everything but reserved; of its
+ * eready_state applied and soft_dirty; d_snaps[g]; the appended or restored
+ * d_ents slots; d_res; d_msgs below *n_msgs.  Only the words that changed are
+ * stored.  Nothing of a group that no record names.  d_msgs == NULL fills
+ * d_res and the counters and modifies nothing else.  *n_appended = the entries
+ * appended, *n_restored = the EFOLLOW_RESTORED records (all three nullable).
+ * d_src may be d_ents itself (in process a leader's msgApp names its own
+ * window).  The source ranges must not overlap the named groups' windows, and
+ * the windows must not overlap each other: the caller's contract.  So is this:
+ * d_in_snaps must not be d_snaps, nor share a row with it -- a restore stores
+ * d_snaps[g] while other records of the call read their Snapshot.  In process
+ * the leader's snapshot is copied out of its emsg_out record into an array of
+ * its own (etcd_amd/raftfollow.py::msgs_from_out does that).
+ * Checked on the device before anything is modified (then every array is
+ * untouched and the counters are 0):
+ *   EWAL_E_INVAL  the group, adjacency, window and reserved-word checks of
+ *                 evote_step_batch_device; kind not 3 or 7; pad != 0; a source
+ *                 range outside n_src_total, or wrapping; a kind-7 record with
+ *                 snap >= n_in_snaps, with a Nodes range outside n_u64, or
+ *                 with d_rstate or d_snaps NULL
+ *   EWAL_E_NOMEM  a kind-3 record with nlog + n_ents > ents_cap (nlog as the
+ *                 call found it -- exact enough: the run rule lets one record
+ *                 of a run grow the log); a kind-7 record with ents_cap == 0;
+ *                 or the messages exceed msgs_cap (INVAL wins when both occur)
+ * and on the host as in evote_step_batch_device, d_rstate, d_snaps and
+ * d_in_snaps sharing d_groups' rules, d_src and d_u64 d_ents'.  n == 0:
+ * EWAL_OK, counters 0. */
+int efollow_step_batch_device(ewal_ctx *ctx, elead_group *d_groups, elead_prop_state *d_pstate,
+                              evote_state *d_vstate, eready_state *d_rstate /* nullable */, uint64_t G,
+                              elead_snap *d_snaps /* G, nullable, WRITTEN by a restore */,
+                              ewal_entry *d_ents, uint64_t n_ents_total,
+                              const ewal_entry *d_src, uint64_t n_src_total,
+                              const elead_snap *d_in_snaps, uint64_t n_in_snaps,
+                              const uint64_t *d_u64, uint64_t n_u64,
+                              const efollow_msg *d_in, uint64_t n, efollow_result *d_res,
+                              struct emsg_out *d_msgs /* NULL: size query */, uint64_t msgs_cap,
+                              uint64_t *n_msgs, uint64_t *n_appended, uint64_t *n_restored);
+/* For bindings / tests: the sizes of the two records. */
+uint32_t efollow_msg_size(void);
+uint32_t efollow_result_size(void);
 
 /* ---- raft ingress: raftpb.Message.Unmarshal, raft/raftpb/raft.pb.go:407-617
  * (called per POST /raft in etcdserver/etcdhttp/http.go:119-146), batched
