@@ -57,6 +57,8 @@ PANIC_FIRST_ENTRY = 41
 PANIC_LEADER_TO_CANDIDATE = 42
 PANIC_NIL_ENTRY = 43
 PANIC_DOUBLE_CONF = 44
+PANIC_COMPACT_APPLIED = 45
+PANIC_COMPACT_BOUNDS = 46
 UNSUPPORTED_ENCODING = 48
 E_HIP, E_INVAL, E_NOMEM, E_NODEVICE, E_TIMEOUT, E_IO = -1, -2, -3, -4, -5, -6
 
@@ -218,6 +220,23 @@ class FollowResult(C.Structure):   # efollow_result
 FOLLOW_MSG_APP, FOLLOW_MSG_SNAP = 3, 7
 (FOLLOW_NOT_STEPPED, FOLLOW_IGNORED, FOLLOW_NO_CASE, FOLLOW_APPENDED, FOLLOW_REJECTED, FOLLOW_RESTORED,
  FOLLOW_SNAP_STALE, FOLLOW_DEFERRED, FOLLOW_PANICKED) = range(9)
+
+class CompactReq(C.Structure):   # ecompact_req
+    _fields_ = [("group", C.c_uint64), ("flags", C.c_uint64), ("index", C.c_uint64), ("threshold", C.c_uint64),
+                ("data_off", C.c_uint64), ("data_len", C.c_uint64), ("nodes_off", C.c_uint64), ("n_nodes", C.c_uint64),
+                ("removed_off", C.c_uint64), ("n_removed", C.c_uint64), ("pad", C.c_uint64 * 2)]
+
+
+class CompactResult(C.Structure):   # ecompact_result
+    _fields_ = [("status", C.c_int32), ("action", C.c_int32), ("index", C.c_uint64), ("term", C.c_uint64),
+                ("n_left", C.c_uint64), ("shift", C.c_uint64), ("src_first", C.c_uint64), ("dst_first", C.c_uint64),
+                ("unstable", C.c_uint64)]
+
+
+# ecompact_req.flags, ecompact_batch_device's flags, ecompact_result.action
+COMPACT_AT_APPLIED = 1
+COMPACT_PEEK = 1
+COMPACT_NOT_STEPPED, COMPACT_NOT_DUE, COMPACT_COMPACTED, COMPACT_PANICKED = range(4)
 
 SNAP_FIELD_DATA, SNAP_FIELD_UNREC, SNAP_FIELD_NODES, SNAP_FIELD_REMOVED = range(4)
 SEG_UNREC, SEG_ENTRY_UNREC, SEG_ENTRY_DATA, SEG_SNAP_UNREC, SEG_SNAP_DATA, SEG_SNAP_NODE, SEG_SNAP_REMOVED = range(7)
@@ -449,6 +468,10 @@ _SIGS = {
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "efollow_msg_size": (C.c_uint32, []),
     "efollow_result_size": (C.c_uint32, []),
+    "ecompact_batch_device": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp,
+                                        C.c_uint64, vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ecompact_req_size": (C.c_uint32, []),
+    "ecompact_result_size": (C.c_uint32, []),
 }
 for _name, (_res, _args) in _SIGS.items():
     if os.environ.get("EWAL_LIB_PATH") and not hasattr(lib, _name):
@@ -480,7 +503,7 @@ def header_symbols(path=HEADER):
     """Every function declared in include/ewal.h."""
     txt = open(path).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead|vote|ready|follow)_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead|vote|ready|follow|compact)_[a-z0-9_]+)\s*\(", txt)))
 
 
 def status_string(st):
@@ -511,6 +534,6 @@ def check(st, detail=0, record=-1, offset=-1):
         return
     if st == E_NODEVICE:
         raise NoDeviceError(st)
-    if 32 <= st <= 44:
+    if 32 <= st <= 46:
         raise GoPanic(st, detail, record, offset)
     raise EwalError(st, detail, record, offset)

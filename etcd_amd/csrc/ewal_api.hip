@@ -38,6 +38,7 @@
 #include "vote_step.hip"
 #include "ready_step.hip"
 #include "follow_step.hip"
+#include "compact_step.hip"
 #include "ewal_stage.h"
 #include "ewal_wire.h"
 
@@ -210,6 +211,10 @@ struct ewal_ctx {
   // groups' claims, the runs' message counts and copy descriptors,
   // per-workgroup partial sums of both
   DevBuf lfollow;
+  // batched log compaction (ecompact_batch_device): two head words, the
+  // groups' claims, the move descriptors, per-workgroup partial sums of both
+  // move classes; and the overlapping class's entries in flight
+  DevBuf lcompact, lcompact_stage;
   std::vector<uint64_t> bent_first, bnents;   // per shard: first ent in bents, count
   std::vector<std::vector<ewal_unrec>> bunrec;       // per shard replayed alone: its XXX_unrecognized side list
   std::vector<std::vector<uint8_t>> bunrec_bytes;
@@ -3830,6 +3835,103 @@ int efollow_step_batch_device(ewal_ctx *c, elead_group *d_groups, elead_prop_sta
   if (n_msgs) *n_msgs = h[0].n_msgs;
   if (n_appended) *n_appended = h[1].n_msgs;
   if (n_restored) *n_restored = h[0].n_committed;
+  return EWAL_OK;
+}
+
+uint32_t ecompact_req_size(void) { return sizeof(ecompact_req); }
+uint32_t ecompact_result_size(void) { return sizeof(ecompact_result); }
+
+static_assert(sizeof(ecompact_req) == 96 && sizeof(ecompact_result) == 64 && sizeof(EcompactMove) == 48 &&
+                  offsetof(ecompact_req, data_off) == 32 && offsetof(ecompact_req, removed_off) == 64 &&
+                  offsetof(ecompact_result, n_left) == 24 && offsetof(ecompact_result, unstable) == 56 &&
+                  offsetof(eready_state, applied) == 48 && offsetof(elead_group, log_offset) == 24 &&
+                  offsetof(elead_prop_state, unstable) == 8,
+              "ecompact layout");
+int ecompact_batch_device(ewal_ctx *c, elead_group *d_groups, elead_prop_state *d_pstate, const eready_state *d_rstate,
+                          uint64_t G, elead_snap *d_snaps, ewal_entry *d_ents, uint64_t n_ents_total,
+                          uint64_t data_len_total, uint64_t n_u64, const ecompact_req *d_reqs, uint64_t n,
+                          ecompact_result *d_res, uint32_t flags, uint64_t *n_compacted, uint64_t *n_moved) {
+  if (n_compacted) *n_compacted = 0;
+  if (n_moved) *n_moved = 0;
+  if (!c) return EWAL_E_INVAL;
+  if (n >= 0x7fffffffull || G >= 0x7fffffffull || (flags & ~(uint32_t)ECOMPACT_PEEK) != 0) return EWAL_E_INVAL;
+  if (n == 0) return EWAL_OK;
+  if (!d_groups || !d_pstate || !d_rstate || !d_snaps || !d_reqs || !d_res || (n_ents_total && !d_ents))
+    return EWAL_E_INVAL;
+  if ((((uintptr_t)d_groups | (uintptr_t)d_pstate | (uintptr_t)d_rstate | (uintptr_t)d_snaps | (uintptr_t)d_reqs |
+        (uintptr_t)d_res) &
+       15) != 0 ||
+      ((uintptr_t)d_ents & 7) != 0)
+    return EWAL_E_INVAL;
+  EW_CHECK(hipSetDevice(c->device));
+  forget_records(c);
+  // scratch: head | overlap head | claim[G] | mv[n] | dpart[2 * workgroups] | opart[2 * workgroups]
+  const uint32_t blocks = grid_for(n, 256);
+  const size_t o_ohead = 64, o_claim = 128, o_mv = (o_claim + (size_t)G * 4 + 15) & ~(size_t)15,
+               o_dpart = o_mv + (size_t)n * sizeof(EcompactMove), o_opart = o_dpart + (size_t)blocks * 16;
+  EW_CHECK(c->lcompact.ensure(o_opart + (size_t)blocks * 16));
+  uint8_t *base = c->lcompact.as<uint8_t>();
+  EcompactArgs a{};
+  a.p.groups = d_groups;
+  a.p.state = d_pstate;
+  a.p.G = G;
+  a.p.ents = d_ents;
+  a.p.n_ents_total = n_ents_total;
+  a.p.data_len_total = data_len_total;
+  a.p.n = n;
+  a.p.head = (EleadHead *)base;
+  a.p.claim = (uint32_t *)(base + o_claim);
+  a.rstate = d_rstate;
+  a.snaps = d_snaps;
+  a.n_u64 = n_u64;
+  a.in = d_reqs;
+  a.n = n;
+  a.res = d_res;
+  a.mv = (EcompactMove *)(base + o_mv);
+  a.dpart = (unsigned long long *)(base + o_dpart);
+  a.opart = (unsigned long long *)(base + o_opart);
+  a.ohead = (EleadHead *)(base + o_ohead);
+  a.blocks = blocks;
+  EW_CHECK(hipEventRecord(c->ev0, c->stream));
+  EW_CHECK(hipMemsetAsync(base, 0, 128, c->stream));
+  if (G) EW_CHECK(hipMemsetAsync(a.p.claim, 0xff, (size_t)G * 4, c->stream));
+  hipLaunchKernelGGL(k_compact_count, dim3(blocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.dpart, blocks, a.p.head);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.opart, blocks, a.ohead);
+  EW_CHECK(hipGetLastError());
+  // the one decision point: nothing of the caller's has been modified yet
+  uint8_t hb[128];
+  EW_CHECK(hipMemcpyAsync(hb, base, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  EleadHead h[2];
+  std::memcpy(&h[0], hb, sizeof(EleadHead));
+  std::memcpy(&h[1], hb + o_ohead, sizeof(EleadHead));
+  if (h[0].errflag & ECOMPACT_ERR_INVAL) return EWAL_E_INVAL;
+  const uint64_t n_dis = h[0].n_msgs, n_ov = h[1].n_msgs;
+  if (flags & ECOMPACT_PEEK) {
+    hipLaunchKernelGGL(k_compact_apply<false>, dim3(blocks), dim3(256), 0, c->stream, a);
+  } else {
+    if (n_ov) {
+      EW_CHECK(c->lcompact_stage.ensure((size_t)n_ov * sizeof(ewal_entry)));
+      a.stage = c->lcompact_stage.as<ewal_entry>();
+    }
+    // the apply pass reads the snapshot's term where the call found it: before any move
+    hipLaunchKernelGGL(k_compact_apply<true>, dim3(blocks), dim3(256), 0, c->stream, a);
+    if (n_dis) {
+      a.n_move = n_dis;
+      hipLaunchKernelGGL(k_compact_move<MV_DIRECT>, dim3(grid_for(n_dis, 256)), dim3(256), 0, c->stream, a);
+    }
+    if (n_ov) {
+      a.n_move = n_ov;
+      hipLaunchKernelGGL(k_compact_move<MV_GATHER>, dim3(grid_for(n_ov, 256)), dim3(256), 0, c->stream, a);
+      hipLaunchKernelGGL(k_compact_move<MV_SCATTER>, dim3(grid_for(n_ov, 256)), dim3(256), 0, c->stream, a);
+    }
+  }
+  EW_CHECK(hipGetLastError());
+  EW_CHECK(hipEventRecord(c->ev1, c->stream));
+  EW_CHECK(hipStreamSynchronize(c->stream));
+  if (n_compacted) *n_compacted = h[0].n_committed;
+  if (n_moved) *n_moved = n_dis + n_ov;
   return EWAL_OK;
 }
 

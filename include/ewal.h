@@ -51,6 +51,8 @@ enum {
   EWAL_PANIC_LEADER_TO_CANDIDATE = 42, /* panic("invalid transition [leader -> candidate]"), raft/raft.go:320 */
   EWAL_PANIC_NIL_ENTRY = 43,       /* at(lastIndex()) is nil and is dereferenced, raft/log.go:137-138 */
   EWAL_PANIC_DOUBLE_CONF = 44,     /* panic("unexpected double uncommitted config entry"), raft/raft.go:344 */
+  EWAL_PANIC_COMPACT_APPLIED = 45, /* panic("raft: compact index (%d) exceeds applied index (%d)"), raft/raft.go:523-525 */
+  EWAL_PANIC_COMPACT_BOUNDS = 46,  /* panic("compact %d out of bounds [%d:%d]"), raft/log.go:162-164 */
   EWAL_UNSUPPORTED_ENCODING = 48,  /* protobuf groups nested deeper than the device
                                       walker's stack; reported, never guessed */
   /* infrastructure (negative) */
@@ -1259,7 +1261,10 @@ typedef struct eready_result {      /* 96 bytes; a DEVICE array of n */
  *     order, as everywhere else.
  *   rd.Snapshot: raftLog.snapshot.Index is d_snaps[g].index (0 when d_snaps ==
  *     NULL); EREADY_SNAP iff it differs from snapi and is not 0.  The snapshot
- *     is d_snaps[g]; saving it is esnap_save_*'s job and the caller's.
+ *     is d_snaps[g]; saving it is esnap_save_*'s job and the caller's.  On the
+ *     device d_snaps[g] is written by a follower's restore and by
+ *     ecompact_batch_device (below): after a compaction the next call here
+ *     reports EREADY_SNAP on its own.
  *   EREADY_UPDATES = containsUpdates() without its Messages term (node.go:
  *     83-86): the messages are the step calls' emsg_out output, the caller
  *     knows their count, and accepting a group that has only messages changes
@@ -1417,6 +1422,8 @@ typedef struct efollow_result {     /* 96 bytes; a DEVICE array of n */
  *     are untouched; the response carries index = lastIndex() = s.index.
  *     r.removed from RemovedNodes stays the caller's, as removed[] does
  *     everywhere: EFOLLOW_RESTORED tells it.
+ *     The leader's d_snaps[g] that a msgSnap carries has a device-side writer
+ *     too: ecompact_batch_device (below).
  * EWAL_UNSUPPORTED_ENCODING, reported, never guessed: the first record of a
  * group with n_peers > 7; a restore with n_nodes > 64 or more than 7 distinct
  * ids; a restore while evote_state.voted != 0 (unreachable in Go: every way of
@@ -1468,6 +1475,117 @@ int efollow_step_batch_device(ewal_ctx *ctx, elead_group *d_groups, elead_prop_s
 /* For bindings / tests: the sizes of the two records. */
 uint32_t efollow_msg_size(void);
 uint32_t efollow_result_size(void);
+
+/* ---- log compaction: node.Compact (raft/node.go:226-227, 325-330), that is
+ * raft.compact (raft/raft.go:522-531) with raftLog.term (raft/log.go:119-124),
+ * raftLog.snap (:171-179) and raftLog.compact (:156-169) under
+ * isOutOfAppliedBounds (:219-224); the policy that says when it is due is
+ * raftLog.shouldCompact (:181-183), its caller EtcdServer.snapshot
+ * (etcdserver/server.go:313-316, 562-571).  Batched over n requests, at most
+ * one per group, for G raft groups on the records the calls above share -- the
+ * step that gives a window's room back and that produces the d_snaps[g] a
+ * leader ships as msgSnap.  A group is its elead_group, its elead_prop_state
+ * and (read only) its eready_state; its log is the window d_ents[ents_first,
+ * + ents_cap).  All arithmetic is Go's uint64 and wraps; lastIndex = nlog - 1 +
+ * log_offset. */
+#define ECOMPACT_AT_APPLIED 1u      /* ecompact_req.flags bit 0 */
+#define ECOMPACT_PEEK 1u            /* ecompact_batch_device's flags bit 0 */
+typedef struct ecompact_req {       /* 96 bytes; one request; a DEVICE array of n */
+  uint64_t group;                   /* which group compacts */
+  uint64_t flags;                   /* bit 0: ECOMPACT_AT_APPLIED; every other bit 0 */
+  uint64_t index;                   /* node.Compact's index; 0 with ECOMPACT_AT_APPLIED */
+  uint64_t threshold;               /* ECOMPACT_AT_APPLIED: raftLog.compactThreshold; otherwise not looked at */
+  uint64_t data_off, data_len;      /* Snapshot.Data = d_data[data_off, + data_len) */
+  uint64_t nodes_off, n_nodes;      /* Snapshot.Nodes = d_u64[nodes_off, + n_nodes) */
+  uint64_t removed_off, n_removed;  /* Snapshot.RemovedNodes = d_u64[removed_off, + n_removed); the four mean
+                                       what elead_snap's fields mean */
+  uint64_t pad[2];                  /* 0 */
+} ecompact_req;
+enum { ECOMPACT_NOT_STEPPED = 0,    /* never reported by this call: a zeroed result row */
+       ECOMPACT_NOT_DUE = 1,        /* ECOMPACT_AT_APPLIED: shouldCompact is false */
+       ECOMPACT_COMPACTED = 2,      /* raft.compact returned */
+       ECOMPACT_PANICKED = 3 };     /* Go panics (status says where), or the request is unsupported */
+typedef struct ecompact_result {    /* 64 bytes; a DEVICE array of n */
+  int32_t status, action;           /* EWAL_OK, an EWAL_PANIC_ class, EWAL_UNSUPPORTED_ENCODING; ECOMPACT_* */
+  uint64_t index, term;             /* the snapshot's Index and Term */
+  uint64_t n_left;                  /* raftLog.compact's return value: len(ents) afterwards */
+  uint64_t shift;                   /* the entries dropped: index - the old log_offset */
+  uint64_t src_first, dst_first;    /* the survivors lay at d_ents[src_first, + n_left) and lie at
+                                       d_ents[dst_first, + n_left) now: ents_first + shift, ents_first */
+  uint64_t unstable;                /* raftLog.unstable after the request */
+} ecompact_result;
+/* Per request, in Go's order:
+ *   The index.  With ECOMPACT_AT_APPLIED the request restates shouldCompact
+ *     with the caller's threshold: when (applied - log_offset) > threshold is
+ *     false (the subtraction wraps, as Go's does) the action is
+ *     ECOMPACT_NOT_DUE with status EWAL_OK, every other result field is 0 and
+ *     nothing changes; otherwise the index is eready_state.applied, where
+ *     EtcdServer.snapshot compacts.  Without the flag the index is req.index.
+ *   raft.compact: index > applied is EWAL_PANIC_COMPACT_APPLIED.
+ *   term = raftLog.term(index): d_ents[ents_first + (index - log_offset)].term,
+ *     or 0 when isOutOfBounds holds; EWAL_PANIC_BOUNDS where at() indexes past
+ *     ents (an empty log at offset 0).
+ *   raftLog.compact: index < log_offset is EWAL_PANIC_COMPACT_BOUNDS (after the
+ *     check above that is all isOutOfAppliedBounds has left).  ents =
+ *     slice(index, lastIndex + 1): where Go's slice is nil -- index > lastIndex,
+ *     which needs applied > lastIndex and which no sequence of this library's
+ *     calls produces, or lastIndex + 1 wrapping to 0 -- Go is left with a
+ *     zero-length log; that is EWAL_UNSUPPORTED_ENCODING, reported, never
+ *     guessed.  Otherwise, with shift = index - log_offset: n_left = nlog -
+ *     shift, elead_prop_state.unstable = max(index + 1, unstable), log_offset =
+ *     index, nlog = n_left, and THE SURVIVORS ARE MOVED TO THE WINDOW'S BASE:
+ *     d_ents[ents_first + j] = the old d_ents[ents_first + shift + j], j <
+ *     n_left, whole 40-byte entries, bit for bit.  ents_first and ents_cap do
+ *     not change.  Go reslices; a fixed window has to slide, or the room never
+ *     comes back: every observable of the log (offset, len, each entry,
+ *     unstable) is Go's.  shift == 0 is legal and moves nothing: only the
+ *     snapshot is replaced.  The slots past n_left keep what they held.
+ *   raftLog.snap: d_snaps[g] = {index, term, data_off, data_len, nodes_off,
+ *     n_nodes, removed_off, n_removed}; r.removedNodes() comes from the request,
+ *     as removed[] is the caller's everywhere.  ECOMPACT_COMPACTED.
+ * Go assigns the snapshot before raftLog.compact can panic; here a panicking
+ * group is left exactly as it was, d_snaps[g] included, as in every other call
+ * -- the process in Go is dead at that point.  A panicking or unsupported
+ * request has action ECOMPACT_PANICKED, every other result field but status 0,
+ * and nothing of its group is modified.
+ * Written: of a compacted group log_offset and nlog, of its elead_prop_state
+ * unstable (only the words that changed), d_snaps[g], the moved d_ents slots;
+ * d_res.  eready_state and evote_state are never written: the next
+ * eready_batch_device reports EREADY_SNAP on its own, because d_snaps[g].index
+ * != snapi.  Groups that no request names are untouched.  With ECOMPACT_PEEK in
+ * flags d_res and the counters are filled and nothing else is modified; a peek
+ * with ECOMPACT_AT_APPLIED finds the due groups, so that the host has
+ * Snapshot.Data made for exactly those and the second call carries their data
+ * ranges.  *n_compacted = the ECOMPACT_COMPACTED requests, *n_moved = the
+ * entries moved (both nullable).
+ * The windows [ents_first, + ents_cap) of the named groups must not overlap
+ * each other: the caller's contract, not checked.  So is this: views of a
+ * compacted group's window taken before the call go stale -- emsg_out
+ * .ents_first, eready_result's views, efollow_msg ranges with d_src == d_ents.
+ * The caller marshals or saves first.
+ * Checked on the device before anything is modified (then every array is
+ * untouched and the counters are 0):
+ *   EWAL_E_INVAL  group >= G; a group named twice; a flags bit other than bit
+ *                 0; pad != 0; ECOMPACT_AT_APPLIED with index != 0; a Data
+ *                 range outside data_len_total, a Nodes or RemovedNodes range
+ *                 outside n_u64, or any of them wrapping; and the group, window
+ *                 and reserved-word checks of elead_local_batch_device
+ * and on the host: NULL arguments (d_ents only when n_ents_total != 0), the
+ * record arrays not 16-byte aligned, d_ents not 8-byte aligned, a bit of flags
+ * other than ECOMPACT_PEEK, n or G >= 2^31 - 1: EWAL_E_INVAL.  EWAL_E_NOMEM
+ * only when the ctx's own staging cannot grow.  n == 0: EWAL_OK, counters 0.  A
+ * compute call on the ctx's stream; ewal_last_device_ms covers it; a repeated
+ * call of the same or a smaller shape allocates nothing. */
+int ecompact_batch_device(ewal_ctx *ctx, elead_group *d_groups, elead_prop_state *d_pstate,
+                          const eready_state *d_rstate, uint64_t G,
+                          elead_snap *d_snaps /* G, WRITTEN */,
+                          ewal_entry *d_ents, uint64_t n_ents_total, uint64_t data_len_total, uint64_t n_u64,
+                          const ecompact_req *d_reqs, uint64_t n, ecompact_result *d_res,
+                          uint32_t flags /* ECOMPACT_PEEK = 1 */,
+                          uint64_t *n_compacted, uint64_t *n_moved /* entries moved; both nullable */);
+/* For bindings / tests: the sizes of the two records. */
+uint32_t ecompact_req_size(void);
+uint32_t ecompact_result_size(void);
 
 /* ---- raft ingress: raftpb.Message.Unmarshal, raft/raftpb/raft.pb.go:407-617
  * (called per POST /raft in etcdserver/etcdhttp/http.go:119-146), batched
