@@ -19,7 +19,7 @@
 //                    n_left).  The moved entries are block-scanned per class;
 //                    the workgroup's sums go to dpart[] (with the COMPACTED
 //                    requests) and opart[].
-//   k_lead_scan      lead_step.hip's, twice: the workgroups' offsets of both
+//   k_lead_scan      step_common.hip's, twice: the workgroups' offsets of both
 //                    classes and the totals.  The host reads the flag word and
 //                    the totals here -- the one decision point.
 //   k_compact_apply  one lane per request again: d_res, and of a COMPACTED
@@ -38,16 +38,14 @@
 //                    <MV_SCATTER>, a launch of its own, stores them at their
 //                    targets.  A launch with no work is skipped.
 //
-// Included by ewal_api.hip after follow_step.hip: lead_prop.hip's group loader
-// and checks, lead_step.hip's claim word, block scan and scan kernel,
-// log_append.hip's block sums and ready_step.hip's offset search are used.
+// Uses step_common.hip, lead_prop.hip's group loader and checks and
+// ready_step.hip's offset search.
 #include "ewal_device.h"
 #include "ewal_internal.h"
 #include "compact_step.h"
 
 namespace cs = compact_step;
 
-#define ECOMPACT_ERR_INVAL 1u
 #define MV_DIRECT 0
 #define MV_GATHER 1
 #define MV_SCATTER 2
@@ -80,24 +78,12 @@ struct EcompactRec {
   uint64_t group, flags, index, threshold, data_off, data_len, nodes_off, n_nodes, removed_off, n_removed, pad0, pad1;
 };
 
-// The wave's 64 requests (6 KiB) as six coalesced 16-B loads per lane,
-// transposed through the wave's 6 KiB of LDS (as follow_step.hip's loader).
+// the wave's 64 requests: lane l gets request r0 + l
 __device__ __forceinline__ EcompactRec ecompact_load_wave(const ecompact_req *__restrict__ in, uint64_t n, el_v2 *s_wave,
                                                           uint64_t r0, uint32_t lane) {
-  const el_v2 *src = (const el_v2 *)(in + r0);
-  const uint64_t left = r0 < n ? (n - r0 < 64 ? n - r0 : 64) * 6 : 0;   // 16-B units of this wave
-  el_v2 x[6];
-#pragma unroll
-  for (uint32_t k = 0; k < 6; ++k) {
-    const uint32_t i = k * 64 + lane;
-    x[k] = i < left ? src[i] : el_v2{0, 0};
-  }
-#pragma unroll
-  for (uint32_t k = 0; k < 6; ++k) s_wave[k * 64 + lane] = x[k];
-  __syncthreads();
-  const el_v2 *q = s_wave + lane * 6;
-  const el_v2 a = q[0], b = q[1], c = q[2], d = q[3], e = q[4], f = q[5];
-  return EcompactRec{a.x, a.y, b.x, b.y, c.x, c.y, d.x, d.y, e.x, e.y, f.x, f.y};
+  el_v2 u[6];
+  step_load_wave(in, n, s_wave, r0, lane, u);
+  return EcompactRec{u[0].x, u[0].y, u[1].x, u[1].y, u[2].x, u[2].y, u[3].x, u[3].y, u[4].x, u[4].y, u[5].x, u[5].y};
 }
 
 __device__ __forceinline__ bool ecompact_range_ok(uint64_t off, uint64_t len, uint64_t total) {
@@ -122,22 +108,20 @@ __device__ __forceinline__ cs::Out ecompact_decide(const EcompactArgs &a, const 
 
 __global__ __launch_bounds__(256) void k_compact_count(const EcompactArgs a) {
   __shared__ el_v2 s_rec[4][384];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint64_t r0 = (uint64_t)blockIdx.x * 256 + wave * 64;
-  const uint64_t i = r0 + lane;
+  const auto [lane, wave, r0, i] = step_lane();
   const EcompactRec r = ecompact_load_wave(a.in, a.n, s_rec[wave], r0, lane);
   const bool valid = i < a.n;
   uint32_t err = 0;
   unsigned long long ncompacted = 0;
   EcompactMove mv{0, cs::MOVE_NONE, 0, 0, 0, 0};
-  if (valid && !ecompact_rec_ok(a, r)) err = ECOMPACT_ERR_INVAL;
+  if (valid && !ecompact_rec_ok(a, r)) err = STEP_ERR_INVAL;
   if (valid && !err) {
     lp::State s;
     uint64_t cap = 0;
     const uint64_t reserved = eprop_load_group(a.p, r.group, s, &cap);
     // the group's claim: a second request for the group finds the word taken
-    if (atomicMin(a.p.claim + r.group, (uint32_t)i) != ELEAD_NOCLAIM) err = ECOMPACT_ERR_INVAL;
-    if (!eprop_group_ok(a.p, s, cap, reserved)) err = ECOMPACT_ERR_INVAL;
+    if (!step_claim(a.p.claim, r.group, i)) err = STEP_ERR_INVAL;
+    if (!eprop_group_ok(a.p, s, cap, reserved)) err = STEP_ERR_INVAL;
     if (!err) {
       const cs::Out o = ecompact_decide(a, r, s);
       if (o.action == cs::COMPACTED) {
@@ -149,31 +133,27 @@ __global__ __launch_bounds__(256) void k_compact_count(const EcompactArgs a) {
       }
     }
   }
-  if (__ballot(err != 0)) {
-    if (err) atomicOr(&a.p.head->errflag, err);
-  }
+  step_flag(a.p.head, err);
   const unsigned long long nd = mv.cls == cs::MOVE_DISJOINT ? mv.cnt : 0;
   const unsigned long long no = mv.cls == cs::MOVE_OVERLAP ? mv.cnt : 0;
   unsigned long long total = 0;
-  mv.loc_d = elead_block_scan(nd, &total);
-  mv.loc_o = elead_block_scan(no, &total);
+  mv.loc_d = step_block_scan(nd, &total);
+  mv.loc_o = step_block_scan(no, &total);
   if (valid) {
     el_v2 *q = (el_v2 *)(a.mv + i);
     q[0] = el_v2{mv.cnt, mv.cls};
     q[1] = el_v2{mv.src, mv.dst};
     q[2] = el_v2{mv.loc_d, mv.loc_o};
   }
-  elog_block_sums(nd, ncompacted, a.dpart, blockIdx.x);
+  step_block_sums(nd, ncompacted, a.dpart, blockIdx.x);
   __syncthreads();                                   // the sums' staging words are reused
-  elog_block_sums(no, 0, a.opart, blockIdx.x);
+  step_block_sums(no, 0, a.opart, blockIdx.x);
 }
 
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_compact_apply(const EcompactArgs a) {
   __shared__ el_v2 s_rec[4][384];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint64_t r0 = (uint64_t)blockIdx.x * 256 + wave * 64;
-  const uint64_t i = r0 + lane;
+  const auto [lane, wave, r0, i] = step_lane();
   const EcompactRec r = ecompact_load_wave(a.in, a.n, s_rec[wave], r0, lane);
   if (i >= a.n) return;
   lp::State s;

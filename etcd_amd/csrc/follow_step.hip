@@ -23,7 +23,7 @@
 //                   copied entries into cpart[].  A later record of the run
 //                   that fails its checks ends the replay before any of its
 //                   ranges is read.
-//   k_lead_scan     lead_step.hip's, twice: the workgroups' message offsets and
+//   k_lead_scan     step_common.hip's, twice: the workgroups' message offsets and
 //                   copy offsets and the totals.  The host reads the flag word
 //                   and the totals here -- the one decision point.
 //   k_follow_apply  one lane per record again: a workgroup-wide exclusive scan
@@ -40,16 +40,13 @@
 //                   pass does) and moves one 40-B ewal_entry, data_off rebased.
 //                   A launch of its own: every read of the apply pass is done.
 //
-// Included by ewal_api.hip after vote_step.hip and ready_step.hip, whose group
-// loader and checks, claim word, block scans and offset search it uses.
+// Uses step_common.hip, lead_prop.hip's and vote_step.hip's group loaders and
+// checks and ready_step.hip's offset search.
 #include "ewal_device.h"
 #include "ewal_internal.h"
 #include "follow_step.h"
 
 namespace fs = follow_step;
-
-#define EFOLLOW_ERR_INVAL 1u
-#define EFOLLOW_ERR_NOMEM 2u
 
 struct EfollowCopy {                // 48 bytes per record; cnt == 0 unless the record heads a run that appends
   unsigned long long cnt, loc;      // the run's copied entries; their offset within its workgroup
@@ -84,34 +81,23 @@ struct EfollowRec {
   uint64_t group, kind, from, term, index, log_term, commit, ents_first, n_ents, data_delta, snap, pad;
 };
 
-__device__ __forceinline__ EfollowRec efollow_unpack(const el_v2 a, const el_v2 b, const el_v2 c, const el_v2 d,
-                                                     const el_v2 e, const el_v2 f) {
-  return EfollowRec{a.x, a.y, b.x, b.y, c.x, c.y, d.x, d.y, e.x, e.y, f.x, f.y};
+__device__ __forceinline__ EfollowRec efollow_unpack(const el_v2 (&u)[6]) {
+  return EfollowRec{u[0].x, u[0].y, u[1].x, u[1].y, u[2].x, u[2].y, u[3].x, u[3].y, u[4].x, u[4].y, u[5].x, u[5].y};
 }
 
-// The wave's 64 records (6 KiB) as six coalesced 16-B loads per lane,
-// transposed through the wave's 6 KiB of LDS (as vote_step.hip's loader).
+// the wave's 64 records: lane l gets record r0 + l
 __device__ __forceinline__ EfollowRec efollow_load_wave(const efollow_msg *__restrict__ in, uint64_t n, el_v2 *s_wave,
                                                         uint64_t r0, uint32_t lane) {
-  const el_v2 *src = (const el_v2 *)(in + r0);
-  const uint64_t left = r0 < n ? (n - r0 < 64 ? n - r0 : 64) * 6 : 0;   // 16-B units of this wave
-  el_v2 x[6];
-#pragma unroll
-  for (uint32_t k = 0; k < 6; ++k) {
-    const uint32_t i = k * 64 + lane;
-    x[k] = i < left ? src[i] : el_v2{0, 0};
-  }
-#pragma unroll
-  for (uint32_t k = 0; k < 6; ++k) s_wave[k * 64 + lane] = x[k];
-  __syncthreads();
-  const el_v2 *q = s_wave + lane * 6;
-  return efollow_unpack(q[0], q[1], q[2], q[3], q[4], q[5]);
+  el_v2 u[6];
+  step_load_wave(in, n, s_wave, r0, lane, u);
+  return efollow_unpack(u);
 }
 
 // One record at an arbitrary place (a run's later records).
 __device__ __forceinline__ EfollowRec efollow_load_rec(const efollow_msg *p) {
-  const el_v2 *src = (const el_v2 *)p;
-  return efollow_unpack(src[0], src[1], src[2], src[3], src[4], src[5]);
+  el_v2 u[6];
+  step_load_rec(p, u);
+  return efollow_unpack(u);
 }
 
 // The checks of one record (group < G included); a msgSnap's Snapshot comes back in *sn.
@@ -133,12 +119,6 @@ __device__ __forceinline__ bool efollow_rec_ok(const EfollowArgs &a, const Efoll
     *nodes_off = q2.x;
   }
   return true;
-}
-
-__device__ __forceinline__ bool efollow_is_head(const EfollowArgs &a, uint64_t i, uint64_t group, uint32_t lane) {
-  uint64_t prev = __shfl_up(group, 1);
-  if (lane == 0 && i > 0 && i < a.n) prev = a.in[i - 1].group;
-  return i < a.n && (i == 0 || prev != group);
 }
 
 // the group's four records as a run's start state
@@ -222,28 +202,8 @@ __device__ __forceinline__ bool efollow_run(const EfollowArgs &a, uint64_t i, co
     if (r.group != g) break;
   }
   if (EMIT) {
-    uint64_t *gw = (uint64_t *)(a.p.groups + g);
-    uint64_t *sw = (uint64_t *)(a.p.state + g);
-    uint64_t *vw = (uint64_t *)(a.vstate + g);
-    if (s.term != s0.term) gw[1] = s.term;
-    if (s.committed != s0.committed) gw[2] = s.committed;
-    if (s.off != s0.off) gw[3] = s.off;
-    if (s.nlog != s0.nlog) gw[4] = s.nlog;
-    if (s.np != s0.np) gw[6] = s.np;
-#pragma unroll
-    for (uint32_t w = 0; w < lp::PEERS; ++w) {
-      if (s.pid[w] != s0.pid[w]) gw[7 + w] = s.pid[w];
-      if (s.match[w] != s0.match[w]) gw[14 + w] = s.match[w];
-      if (s.next[w] != s0.next[w]) gw[21 + w] = s.next[w];
-    }
-    if (s.unstable != s0.unstable) sw[1] = s.unstable;
-    if (s.pending != s0.pending) sw[2] = s.pending;
-    if (v.state != v0.state) vw[0] = v.state;
-    if (v.vote != v0.vote) vw[1] = v.vote;
-    if (v.lead != v0.lead) vw[2] = v.lead;
-    if (v.elapsed != v0.elapsed) vw[3] = v.elapsed;
-    if (v.voted != v0.voted) vw[4] = v.voted;
-    if (v.granted != v0.granted) vw[5] = v.granted;
+    lp_store_changed(a.p.groups, a.p.state, g, s0, s);
+    vs_store_changed(a.vstate, g, v0, v);
     if (run.ov.restored) {                           // efollow_rec_ok: rstate and snaps are there
       uint64_t *rw = (uint64_t *)(a.rstate + g);
       if (rd.applied != rd0.applied) rw[6] = rd.applied;
@@ -263,19 +223,17 @@ __device__ __forceinline__ bool efollow_run(const EfollowArgs &a, uint64_t i, co
 
 __global__ __launch_bounds__(256) void k_follow_count(const EfollowArgs a) {
   __shared__ el_v2 s_rec[4][384];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint64_t r0 = (uint64_t)blockIdx.x * 256 + wave * 64;
-  const uint64_t i = r0 + lane;
+  const auto [lane, wave, r0, i] = step_lane();
   const EfollowRec r = efollow_load_wave(a.in, a.n, s_rec[wave], r0, lane);
   const bool valid = i < a.n;
-  const bool head = efollow_is_head(a, i, r.group, lane);
+  const bool head = step_is_head(a.in, a.n, i, r.group, lane);
   uint32_t err = 0;
   unsigned long long tot = 0, nrest = 0;
   EfollowCopy cp{0, 0, 0, 0, 0, 0};
   if (valid) {
     fs::Snap sn;
     uint64_t nodes_off = 0;
-    if (!efollow_rec_ok(a, r, &sn, &nodes_off)) err = EFOLLOW_ERR_INVAL;
+    if (!efollow_rec_ok(a, r, &sn, &nodes_off)) err = STEP_ERR_INVAL;
   }
   if (head && !err) {
     lp::State s;
@@ -284,25 +242,23 @@ __global__ __launch_bounds__(256) void k_follow_count(const EfollowArgs a) {
     uint64_t cap = 0, vreserved = 0;
     const uint64_t reserved = efollow_load_group(a, r.group, s, v, rd, &cap, &vreserved);
     // the group's claim: the head of a second run finds the word taken
-    if (atomicMin(a.p.claim + r.group, (uint32_t)i) != ELEAD_NOCLAIM) err = EFOLLOW_ERR_INVAL;
-    if (!eprop_group_ok(a.p, s, cap, reserved) || !evote_state_ok(s, v, vreserved)) err = EFOLLOW_ERR_INVAL;
+    if (!step_claim(a.p.claim, r.group, i)) err = STEP_ERR_INVAL;
+    if (!eprop_group_ok(a.p, s, cap, reserved) || !evote_state_ok(s, v, vreserved)) err = STEP_ERR_INVAL;
     if (!err) {
       uint64_t room = 0;
       bool snap_seen = false;
       if (!efollow_run<false, true>(a, i, r, s, v, rd, false, 0, tot, nrest, cp, room, snap_seen)) {
-        err = EFOLLOW_ERR_INVAL;
+        err = STEP_ERR_INVAL;
         tot = nrest = 0;
         cp.cnt = 0;
       } else if (cap - s.nlog < room || (snap_seen && cap == 0)) {
-        err = EFOLLOW_ERR_NOMEM;
+        err = STEP_ERR_NOMEM;
       }
     }
   }
-  if (__ballot(err != 0)) {
-    if (err) atomicOr(&a.p.head->errflag, err);
-  }
+  step_flag(a.p.head, err);
   unsigned long long total = 0;
-  cp.loc = elead_block_scan(cp.cnt, &total);
+  cp.loc = step_block_scan(cp.cnt, &total);
   if (valid) {
     a.run_msgs[i] = tot;
     el_v2 *q = (el_v2 *)(a.cp + i);
@@ -310,21 +266,19 @@ __global__ __launch_bounds__(256) void k_follow_count(const EfollowArgs a) {
     q[1] = el_v2{cp.src, cp.dst};
     q[2] = el_v2{cp.delta, 0};
   }
-  elog_block_sums(tot, nrest, a.p.partial, blockIdx.x);
+  step_block_sums(tot, nrest, a.p.partial, blockIdx.x);
   __syncthreads();                                   // the sums' staging words are reused
-  elog_block_sums(cp.cnt, 0, a.cpart, blockIdx.x);
+  step_block_sums(cp.cnt, 0, a.cpart, blockIdx.x);
 }
 
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_follow_apply(const EfollowArgs a) {
   __shared__ el_v2 s_rec[4][384];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint64_t r0 = (uint64_t)blockIdx.x * 256 + wave * 64;
-  const uint64_t i = r0 + lane;
+  const auto [lane, wave, r0, i] = step_lane();
   const EfollowRec r = efollow_load_wave(a.in, a.n, s_rec[wave], r0, lane);
-  const bool head = efollow_is_head(a, i, r.group, lane);
+  const bool head = step_is_head(a.in, a.n, i, r.group, lane);
   unsigned long long total = 0;
-  const unsigned long long before = elead_block_scan(i < a.n ? a.run_msgs[i] : 0, &total);
+  const unsigned long long before = step_block_scan(i < a.n ? a.run_msgs[i] : 0, &total);
   if (head) {
     lp::State s;
     vs::Vote v;

@@ -30,7 +30,7 @@
 //                 run's last record checks the room for the run's proposals
 //                 (NOMEM).  Per-workgroup sums of messages and appended
 //                 entries into partial[] (no atomics on one address).
-//   k_lead_scan   lead_step.hip's: the workgroups' message offsets and the
+//   k_lead_scan   step_common.hip's: the workgroups' message offsets and the
 //                 totals.  The host reads the flag word and the totals here --
 //                 the one decision point (INVAL, NOMEM, the size query).
 //   k_prop_apply  one lane per record: d_res, and with EMIT the record's own
@@ -50,10 +50,6 @@
 #include "ewal_internal.h"
 #include "lead_prop_step.h"
 
-namespace lp = lead_prop;
-
-#define EPROP_ERR_INVAL 1u
-#define EPROP_ERR_NOMEM 2u
 #define EPROP_SERIAL (1ull << 63)   // cnt[i]: the record's run is serial
 #define EPROP_OPEN (1ull << 63)     // seg[i]: the run started in an earlier workgroup
 #define EPROP_LOW 0xFFFFFFFFull
@@ -86,42 +82,23 @@ struct EpropRec {
   uint64_t group, kind, tn, data_off, data_len;
 };
 
-// The wave's 64 records (3 KiB) as three coalesced 16-B loads per lane,
-// transposed through the wave's 3 KiB of LDS (as elead_load_resp_wave).
+__device__ __forceinline__ EpropRec eprop_unpack(const el_v2 (&u)[3]) {
+  return EpropRec{u[0].x, u[0].y, u[1].x, u[1].y, u[2].x};
+}
+
+// the wave's 64 records: lane l gets record r0 + l
 __device__ __forceinline__ EpropRec eprop_load_wave(const elead_local *__restrict__ locals, uint64_t n, el_v2 *s_wave,
                                                     uint64_t r0, uint32_t lane) {
-  const el_v2 *src = (const el_v2 *)(locals + r0);
-  const uint64_t left = r0 < n ? (n - r0 < 64 ? n - r0 : 64) * 3 : 0;   // 16-B units of this wave
-  el_v2 x[3];
-#pragma unroll
-  for (uint32_t k = 0; k < 3; ++k) {
-    const uint32_t i = k * 64 + lane;
-    x[k] = i < left ? src[i] : el_v2{0, 0};
-  }
-#pragma unroll
-  for (uint32_t k = 0; k < 3; ++k) s_wave[k * 64 + lane] = x[k];
-  __syncthreads();
-  const el_v2 a = s_wave[lane * 3], b = s_wave[lane * 3 + 1], c = s_wave[lane * 3 + 2];
-  EpropRec r;
-  r.group = a.x;
-  r.kind = a.y;
-  r.tn = b.x;
-  r.data_off = b.y;
-  r.data_len = c.x;
-  return r;
+  el_v2 u[3];
+  step_load_wave(locals, n, s_wave, r0, lane, u);
+  return eprop_unpack(u);
 }
 
 // One record at an arbitrary place (a serial run's later records).
 __device__ __forceinline__ EpropRec eprop_load_rec(const elead_local *p) {
-  const el_v2 *src = (const el_v2 *)p;
-  const el_v2 a = src[0], b = src[1], c = src[2];
-  EpropRec r;
-  r.group = a.x;
-  r.kind = a.y;
-  r.tn = b.x;
-  r.data_off = b.y;
-  r.data_len = c.x;
-  return r;
+  el_v2 u[3];
+  step_load_rec(p, u);
+  return eprop_unpack(u);
 }
 
 // The group's record and its state record; returns the OR of the reserved words.
@@ -174,12 +151,7 @@ __device__ __forceinline__ bool eprop_group_ok(const EpropArgs &a, const lp::Sta
   return !dup;
 }
 
-// whether record i starts / ends a run: the wave's edge lanes look at the neighbouring wave's record
-__device__ __forceinline__ bool eprop_is_head(const EpropArgs &a, uint64_t i, uint64_t group, uint32_t lane) {
-  uint64_t prev = __shfl_up(group, 1);
-  if (lane == 0 && i > 0 && i < a.n) prev = a.locals[i - 1].group;
-  return i < a.n && (i == 0 || prev != group);
-}
+// whether record i ends a run (step_is_head's mirror): lane 63 looks at the record after its wave's
 __device__ __forceinline__ bool eprop_is_tail(const EpropArgs &a, uint64_t i, uint64_t group, uint32_t lane) {
   uint64_t nxt = __shfl_down(group, 1);
   if (lane == 63 && i + 1 < a.n) nxt = a.locals[i + 1].group;
@@ -232,31 +204,27 @@ __device__ __forceinline__ unsigned long long eprop_seg_scan(unsigned long long 
 
 __global__ __launch_bounds__(256) void k_prop_check(const EpropArgs a) {
   __shared__ el_v2 s_rec[4][192];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint64_t r0 = (uint64_t)blockIdx.x * 256 + wave * 64;
-  const uint64_t i = r0 + lane;
+  const auto [lane, wave, r0, i] = step_lane();
   const EpropRec r = eprop_load_wave(a.locals, a.n, s_rec[wave], r0, lane);
   const bool valid = i < a.n;
-  const bool head = eprop_is_head(a, i, r.group, lane);
+  const bool head = step_is_head(a.locals, a.n, i, r.group, lane);
   const bool prop = r.kind == lp::KIND_PROP;
   uint32_t err = 0;
   if (valid) {
-    if (r.group >= a.G) err = EPROP_ERR_INVAL;
-    if (r.kind != lp::KIND_BEAT && !prop) err = EPROP_ERR_INVAL;
-    if ((r.tn >> 32) > 1) err = EPROP_ERR_INVAL;     // data_nil
-    if (prop && (r.data_len > a.data_len_total || r.data_off > a.data_len_total - r.data_len)) err = EPROP_ERR_INVAL;
+    if (r.group >= a.G) err = STEP_ERR_INVAL;
+    if (r.kind != lp::KIND_BEAT && !prop) err = STEP_ERR_INVAL;
+    if ((r.tn >> 32) > 1) err = STEP_ERR_INVAL;     // data_nil
+    if (prop && (r.data_len > a.data_len_total || r.data_off > a.data_len_total - r.data_len)) err = STEP_ERR_INVAL;
   }
   if (head && r.group < a.G) {
     lp::State s;
     uint64_t cap = 0;
     const uint64_t reserved = eprop_load_group(a, r.group, s, &cap);
     // the group's claim: the head of a second run finds the word taken
-    if (atomicMin(a.claim + r.group, (uint32_t)i) != ELEAD_NOCLAIM) err = EPROP_ERR_INVAL;
-    if (!eprop_group_ok(a, s, cap, reserved)) err = EPROP_ERR_INVAL;
+    if (!step_claim(a.claim, r.group, i)) err = STEP_ERR_INVAL;
+    if (!eprop_group_ok(a, s, cap, reserved)) err = STEP_ERR_INVAL;
   }
-  if (__ballot(err != 0)) {
-    if (err) atomicOr(&a.head->errflag, err);
-  }
+  step_flag(a.head, err);
   const unsigned long long v =
       (valid && prop) ? 1ull | ((uint32_t)r.tn == (uint32_t)lp::ENTRY_CONF_CHANGE ? 1ull << 32 : 0ull) : 0ull;
   bool seen = false, wg_seen = false;
@@ -400,6 +368,7 @@ __device__ __forceinline__ void eprop_run(const EpropArgs &a, uint64_t i, const 
     if (r.group != g) break;
   }
   if (EMIT) {
+    // lp_store_changed's words, but a peer's match and next go together here
     uint64_t *gw = (uint64_t *)(a.groups + g);
     uint64_t *sw = (uint64_t *)(a.state + g);
     if (s.committed != s0.committed) gw[2] = s.committed;
@@ -417,13 +386,11 @@ __device__ __forceinline__ void eprop_run(const EpropArgs &a, uint64_t i, const 
 
 __global__ __launch_bounds__(256) void k_prop_count(const EpropArgs a) {
   __shared__ el_v2 s_rec[4][192];
-  if (a.head->errflag & EPROP_ERR_INVAL) return;                       // an invalid call: nothing below may trust the records
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint64_t r0 = (uint64_t)blockIdx.x * 256 + wave * 64;
-  const uint64_t i = r0 + lane;
+  if (a.head->errflag & STEP_ERR_INVAL) return;                       // an invalid call: nothing below may trust the records
+  const auto [lane, wave, r0, i] = step_lane();
   const EpropRec r = eprop_load_wave(a.locals, a.n, s_rec[wave], r0, lane);
   const bool valid = i < a.n;
-  const bool head = eprop_is_head(a, i, r.group, lane);
+  const bool head = step_is_head(a.locals, a.n, i, r.group, lane);
   const bool tail = eprop_is_tail(a, i, r.group, lane);
   unsigned long long tot = 0, napp = 0, mode = 0;
   uint32_t err = 0;
@@ -433,7 +400,7 @@ __global__ __launch_bounds__(256) void k_prop_count(const EpropArgs a) {
     lp::State s;
     (void)eprop_load_group(a, r.group, s, &cap);
     eprop_load_snap(a, r.group, s);
-    if (tail && cap - s.nlog < nprops) err = EPROP_ERR_NOMEM;
+    if (tail && cap - s.nlog < nprops) err = STEP_ERR_NOMEM;
     const lp::Run run = lp::prepare(s);
     if (run.closed) {
       if (r.kind == lp::KIND_BEAT) {
@@ -447,25 +414,21 @@ __global__ __launch_bounds__(256) void k_prop_count(const EpropArgs a) {
       if (head) eprop_run<false>(a, i, r, s, false, 0, tot, napp);
     }
   }
-  if (__ballot(err != 0)) {
-    if (err) atomicOr(&a.head->errflag, err);
-  }
+  step_flag(a.head, err);
   if (valid) a.cnt[i] = tot | mode;
-  elog_block_sums(tot, napp, a.partial, blockIdx.x);
+  step_block_sums(tot, napp, a.partial, blockIdx.x);
 }
 
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_prop_apply(const EpropArgs a) {
   __shared__ el_v2 s_rec[4][192];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint64_t r0 = (uint64_t)blockIdx.x * 256 + wave * 64;
-  const uint64_t i = r0 + lane;
+  const auto [lane, wave, r0, i] = step_lane();
   const EpropRec r = eprop_load_wave(a.locals, a.n, s_rec[wave], r0, lane);
   const bool valid = i < a.n;
-  const bool head = eprop_is_head(a, i, r.group, lane);
+  const bool head = step_is_head(a.locals, a.n, i, r.group, lane);
   const unsigned long long c = valid ? a.cnt[i] : 0;
   unsigned long long total = 0;
-  const unsigned long long before = elead_block_scan(c & ~EPROP_SERIAL, &total);
+  const unsigned long long before = step_block_scan(c & ~EPROP_SERIAL, &total);
   const uint64_t msg_first = a.partial[2 * (uint64_t)blockIdx.x] + before;
   if (!valid) return;
   if (c & EPROP_SERIAL) {
@@ -498,9 +461,7 @@ __global__ __launch_bounds__(256) void k_prop_apply(const EpropArgs a) {
 
 __global__ __launch_bounds__(256) void k_prop_commit(const EpropArgs a) {
   __shared__ el_v2 s_rec[4][192];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint64_t r0 = (uint64_t)blockIdx.x * 256 + wave * 64;
-  const uint64_t i = r0 + lane;
+  const auto [lane, wave, r0, i] = step_lane();
   const EpropRec r = eprop_load_wave(a.locals, a.n, s_rec[wave], r0, lane);
   const bool tail = eprop_is_tail(a, i, r.group, lane);
   if (!tail || (a.cnt[i] & EPROP_SERIAL)) return;

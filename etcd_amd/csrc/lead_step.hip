@@ -25,9 +25,9 @@
 //                 messages of the run into run_msgs[head] (0 at the other
 //                 responses) and the workgroup's sums of messages and of
 //                 committing responses into partial[2 b], [2 b + 1].
-//   k_lead_scan   one workgroup: the exclusive prefix sum of the workgroups'
-//                 message counts in place (a thread owns a contiguous chunk of
-//                 them), the two totals into the head words.
+//   k_lead_scan   step_common.hip's, one workgroup: the exclusive prefix sum of
+//                 the workgroups' message counts in place, the two totals
+//                 into the head words.
 //                 The host reads the flag word and the totals here -- the one
 //                 decision point (INVAL, NOMEM, the size query's answer).
 //   k_lead_apply  one lane per response again: a workgroup-wide exclusive scan
@@ -49,16 +49,9 @@
 #include "ewal_device.h"
 #include "ewal_internal.h"
 
-#define ELEAD_ERR_INVAL 1u
-#define ELEAD_NOCLAIM 0xFFFFFFFFu
 #define ELEAD_PEERS 7u
 #define ELEAD_MSGAPP 3u           // raft.msgApp (raft/raft.go:22-34)
 #define ELEAD_MSGSNAP 7u          // raft.msgSnap
-
-struct EleadHead {
-  uint32_t errflag, pad;
-  unsigned long long n_msgs, n_committed;
-};
 
 struct EleadArgs {
   elead_group *groups;
@@ -93,23 +86,12 @@ struct EleadMsg {
   uint64_t type, index, log_term, efirst, nents;
 };
 
-// The wave's 64 response records (3 KiB) as three coalesced 16-B loads per
-// lane, transposed through the wave's 3 KiB of LDS: lane l gets record r0 + l.
-// Every thread of the workgroup calls it (records past n come back as zeros).
+// the wave's 64 response records: lane l gets record r0 + l
 __device__ __forceinline__ EleadResp elead_load_resp_wave(const elead_resp *__restrict__ resps, uint64_t n,
                                                           el_v2 *s_wave, uint64_t r0, uint32_t lane) {
-  const el_v2 *src = (const el_v2 *)(resps + r0);
-  const uint64_t left = r0 < n ? (n - r0 < 64 ? n - r0 : 64) * 3 : 0;   // 16-B units of this wave
-  el_v2 x[3];
-#pragma unroll
-  for (uint32_t k = 0; k < 3; ++k) {
-    const uint32_t i = k * 64 + lane;
-    x[k] = i < left ? src[i] : el_v2{0, 0};
-  }
-#pragma unroll
-  for (uint32_t k = 0; k < 3; ++k) s_wave[k * 64 + lane] = x[k];
-  __syncthreads();
-  const el_v2 a = s_wave[lane * 3], b = s_wave[lane * 3 + 1], c = s_wave[lane * 3 + 2];
+  el_v2 u[3];
+  step_load_wave(resps, n, s_wave, r0, lane, u);
+  const el_v2 a = u[0], b = u[1], c = u[2];
   EleadResp r;
   r.group = a.x;
   r.from = a.y;
@@ -426,97 +408,35 @@ __host__ __device__ __forceinline__ bool elead_group_ok(const EleadArgs &a, cons
   return !dup;
 }
 
-// whether response i starts a run: lane 0 of a wave looks at the record before its wave's
-__device__ __forceinline__ bool elead_is_head(const EleadArgs &a, uint64_t i, uint64_t group, uint32_t lane) {
-  uint64_t prev = __shfl_up(group, 1);
-  if (lane == 0 && i > 0 && i < a.n) prev = a.resps[i - 1].group;
-  return i < a.n && (i == 0 || prev != group);
-}
-
 __global__ __launch_bounds__(256) void k_lead_count(const EleadArgs a) {
   __shared__ el_v2 s_resp[4][192];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint64_t r0 = (uint64_t)blockIdx.x * 256 + wave * 64;
-  const uint64_t i = r0 + lane;
+  const auto [lane, wave, r0, i] = step_lane();
   const EleadResp r = elead_load_resp_wave(a.resps, a.n, s_resp[wave], r0, lane);
-  const bool head = elead_is_head(a, i, r.group, lane);
+  const bool head = step_is_head(a.resps, a.n, i, r.group, lane);
   uint32_t err = 0;
   unsigned long long tot = 0, ncommit = 0;
-  if (i < a.n && r.group >= a.G) err = ELEAD_ERR_INVAL;
+  if (i < a.n && r.group >= a.G) err = STEP_ERR_INVAL;
   if (head && !err) {
     EleadState s;
     const uint64_t reserved = elead_load_group(a.groups + r.group, s);
     // the group's claim: the head of a second run finds the word taken
-    if (atomicMin(a.claim + r.group, (uint32_t)i) != ELEAD_NOCLAIM) err = ELEAD_ERR_INVAL;
-    if (!elead_group_ok(a, s, reserved)) err = ELEAD_ERR_INVAL;
+    if (!step_claim(a.claim, r.group, i)) err = STEP_ERR_INVAL;
+    if (!elead_group_ok(a, s, reserved)) err = STEP_ERR_INVAL;
     if (!err) elead_run<false>(a, i, r, s, false, 0, tot, ncommit);
   }
-  if (__ballot(err != 0)) {
-    if (err) atomicOr(&a.head->errflag, err);      // one atomic a wave (the compiler folds the active lanes)
-  }
+  step_flag(a.head, err);
   if (i < a.n) a.run_msgs[i] = tot;
-  elog_block_sums(tot, ncommit, a.partial, blockIdx.x);
-}
-
-// the workgroup's exclusive prefix sum of v; *total = the workgroup's sum
-__device__ __forceinline__ unsigned long long elead_block_scan(unsigned long long v, unsigned long long *total) {
-  __shared__ unsigned long long s_wsum[4];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  unsigned long long incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long t = __shfl_up(incl, d);
-    if ((int)lane >= d) incl += t;
-  }
-  if (lane == 63) s_wsum[wave] = incl;
-  __syncthreads();
-  unsigned long long base = 0, all = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < 4; ++w) {
-    const unsigned long long x = s_wsum[w];
-    base += w < wave ? x : 0;
-    all += x;
-  }
-  __syncthreads();                                 // s_wsum is free for the next call
-  *total = all;
-  return base + incl - v;
-}
-
-__global__ __launch_bounds__(256) void k_lead_scan(unsigned long long *__restrict__ partial, uint32_t nslots,
-                                                   EleadHead *head) {
-  // thread t owns the workgroups [t * chunk, (t + 1) * chunk)
-  const uint32_t chunk = (nslots + 255u) / 256u;
-  const uint64_t lo = (uint64_t)threadIdx.x * chunk;
-  const uint64_t hi = lo + chunk < nslots ? lo + chunk : nslots;
-  unsigned long long sum = 0, ncommit = 0;
-  for (uint64_t s = lo; s < hi; ++s) {
-    sum += partial[2 * s];
-    ncommit += partial[2 * s + 1];
-  }
-  unsigned long long total = 0, ctotal = 0;
-  unsigned long long at = elead_block_scan(sum, &total);
-  (void)elead_block_scan(ncommit, &ctotal);
-  for (uint64_t s = lo; s < hi; ++s) {
-    const unsigned long long v = partial[2 * s];
-    partial[2 * s] = at;
-    at += v;
-  }
-  if (threadIdx.x == 0) {
-    head->n_msgs = total;
-    head->n_committed = ctotal;
-  }
+  step_block_sums(tot, ncommit, a.partial, blockIdx.x);
 }
 
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_lead_apply(const EleadArgs a) {
   __shared__ el_v2 s_resp[4][192];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint64_t r0 = (uint64_t)blockIdx.x * 256 + wave * 64;
-  const uint64_t i = r0 + lane;
+  const auto [lane, wave, r0, i] = step_lane();
   const EleadResp r = elead_load_resp_wave(a.resps, a.n, s_resp[wave], r0, lane);
-  const bool head = elead_is_head(a, i, r.group, lane);
+  const bool head = step_is_head(a.resps, a.n, i, r.group, lane);
   unsigned long long total = 0;
-  const unsigned long long before = elead_block_scan(i < a.n ? a.run_msgs[i] : 0, &total);
+  const unsigned long long before = step_block_scan(i < a.n ? a.run_msgs[i] : 0, &total);
   if (head) {
     EleadState s;
     (void)elead_load_group(a.groups + r.group, s);

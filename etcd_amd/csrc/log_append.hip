@@ -30,12 +30,7 @@
 #include "ewal_internal.h"
 
 #define ELOG_LANE_MAX 8u          // entries per message the lane-per-message kernel takes
-#define ELOG_ERR_INVAL 1u
-#define ELOG_ERR_NOMEM 2u
-#define ELOG_NOCLAIM 0xFFFFFFFFu
 #define ELOG_MSGAPPRESP 4u        // raft.msgAppResp (raft/raft.go:22-34)
-
-typedef uint64_t el_v2 __attribute__((ext_vector_type(2)));   // 16 bytes
 
 struct ElogHead {
   uint32_t errflag, nlong;
@@ -64,28 +59,16 @@ struct ElogRec {
   uint64_t w[8];
 };
 
-// The wave's 64 app records (4 KiB) as four coalesced 16-B loads per lane,
-// transposed through the wave's 4 KiB of LDS: lane l gets record r0 + l.
-// Every thread of the workgroup calls it (records past n come back as zeros).
+// the wave's 64 app records: lane l gets record r0 + l
 __device__ __forceinline__ ElogRec load_app(const elog_app *__restrict__ apps, uint64_t n, el_v2 *s_wave,
                                             uint64_t r0, uint32_t lane) {
-  const el_v2 *src = (const el_v2 *)(apps + r0);
-  const uint64_t left = r0 < n ? (n - r0 < 64 ? n - r0 : 64) * 4 : 0;   // 16-B units of this wave
-  el_v2 x[4];
-#pragma unroll
-  for (uint32_t k = 0; k < 4; ++k) {
-    const uint32_t i = k * 64 + lane;
-    x[k] = i < left ? src[i] : el_v2{0, 0};
-  }
-#pragma unroll
-  for (uint32_t k = 0; k < 4; ++k) s_wave[k * 64 + lane] = x[k];
-  __syncthreads();
+  el_v2 u[4];
+  step_load_wave(apps, n, s_wave, r0, lane, u);
   ElogRec r;
 #pragma unroll
   for (uint32_t k = 0; k < 4; ++k) {
-    const el_v2 v = s_wave[lane * 4 + k];
-    r.w[2 * k] = v.x;
-    r.w[2 * k + 1] = v.y;
+    r.w[2 * k] = u[k].x;
+    r.w[2 * k + 1] = u[k].y;
   }
   return r;
 }
@@ -123,23 +106,21 @@ __host__ __device__ __forceinline__ ElogRec load_rec(const void *p) {
 
 __global__ __launch_bounds__(256) void k_lapp_check(const ElogArgs a) {
   __shared__ el_v2 s_app[4][256];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint64_t r0 = (uint64_t)blockIdx.x * 256 + wave * 64;
-  const uint64_t i = r0 + lane;
+  const auto [lane, wave, r0, i] = step_lane();
   const ElogRec A = load_app(a.apps, a.n, s_app[wave], r0, lane);
   uint32_t err = 0;
   bool lng = false;
   if (i < a.n) {
     const uint64_t ne = A.w[A_NENTS];
     if (A.w[A_GROUP] >= a.G || ne > a.n_ents_total || A.w[A_FIRST] > a.n_ents_total - ne) {
-      err = ELOG_ERR_INVAL;
+      err = STEP_ERR_INVAL;
     } else {
       const ElogRec g = load_rec(a.groups + A.w[A_GROUP]);
       const uint64_t cap = g.w[G_TCAP], nlog = g.w[G_NLOG];
-      if (cap > a.n_terms || g.w[G_TOFF] > a.n_terms - cap || nlog > cap) err = ELOG_ERR_INVAL;
-      else if (ne > cap - nlog) err = ELOG_ERR_NOMEM;
+      if (cap > a.n_terms || g.w[G_TOFF] > a.n_terms - cap || nlog > cap) err = STEP_ERR_INVAL;
+      else if (ne > cap - nlog) err = STEP_ERR_NOMEM;
       // the group's claim: a second message for it finds the word taken
-      if (atomicMin(a.claim + A.w[A_GROUP], (uint32_t)i) != ELOG_NOCLAIM) err |= ELOG_ERR_INVAL;
+      if (!step_claim(a.claim, A.w[A_GROUP], i)) err |= STEP_ERR_INVAL;
       lng = ne > ELOG_LANE_MAX;
     }
   }
@@ -236,30 +217,6 @@ __host__ __device__ __forceinline__ void elog_finish(const ElogArgs &a, uint64_t
   napp += n_app;
 }
 
-__device__ __forceinline__ unsigned long long elog_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
-// the workgroup's two sums into partial[2 * slot ..]
-__device__ __forceinline__ void elog_block_sums(unsigned long long acc, unsigned long long napp,
-                                                unsigned long long *partial, uint32_t slot) {
-  __shared__ unsigned long long s_sum[4][2];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  acc = elog_wave_sum(acc);
-  napp = elog_wave_sum(napp);
-  if (lane == 0) {
-    s_sum[wave][0] = acc;
-    s_sum[wave][1] = napp;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partial[2 * (uint64_t)slot] = s_sum[0][0] + s_sum[1][0] + s_sum[2][0] + s_sum[3][0];
-    partial[2 * (uint64_t)slot + 1] = s_sum[0][1] + s_sum[1][1] + s_sum[2][1] + s_sum[3][1];
-  }
-}
-
 // One message of at most ELOG_LANE_MAX entries, start to finish, in one lane.
 __host__ __device__ __forceinline__ void elog_lane_message(const ElogArgs &a, uint64_t i, const ElogRec &A,
                                                            unsigned long long &acc, unsigned long long &napp) {
@@ -296,14 +253,12 @@ __host__ __device__ __forceinline__ void elog_lane_message(const ElogArgs &a, ui
 
 __global__ __launch_bounds__(256) void k_lapp_lane(const ElogArgs a) {
   __shared__ el_v2 s_app[4][256];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint64_t r0 = (uint64_t)blockIdx.x * 256 + wave * 64;
-  const uint64_t i = r0 + lane;
+  const auto [lane, wave, r0, i] = step_lane();
   const ElogRec A = load_app(a.apps, a.n, s_app[wave], r0, lane);
   unsigned long long acc = 0, napp = 0;
   const uint64_t ne = A.w[A_NENTS];
   if (i < a.n && ne <= ELOG_LANE_MAX) elog_lane_message(a, i, A, acc, napp);
-  elog_block_sums(acc, napp, a.partial, blockIdx.x);
+  step_block_sums(acc, napp, a.partial, blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void k_lapp_wave(const ElogArgs a, uint32_t nlong) {
@@ -344,7 +299,7 @@ __global__ __launch_bounds__(256) void k_lapp_wave(const ElogArgs a, uint32_t nl
     if (wn)
       for (uint64_t k = wk + lane; k < ne; k += 64) win[pos + 1 + k] = es[k].term;
   }
-  elog_block_sums(acc, napp, a.partial, a.lane_blocks + blockIdx.x);
+  step_block_sums(acc, napp, a.partial, a.lane_blocks + blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void k_lapp_sum(const unsigned long long *__restrict__ partial, uint32_t nslots,
@@ -354,5 +309,5 @@ __global__ __launch_bounds__(256) void k_lapp_sum(const unsigned long long *__re
     acc += partial[2 * (uint64_t)s];
     napp += partial[2 * (uint64_t)s + 1];
   }
-  elog_block_sums(acc, napp, &head->accepted, 0);   // accepted, appended: adjacent words
+  step_block_sums(acc, napp, &head->accepted, 0);   // accepted, appended: adjacent words
 }

@@ -9,7 +9,7 @@
 //                  16-B pieces -- the first 48 B of the elead_group and its
 //                  reserved words, the elead_prop_state, state / vote / lead
 //                  and the reserved words of the evote_state, the eready_state,
-//                  the snapshot's index -- claims the group (lead_step.hip's
+//                  the snapshot's index -- claims the group (step_common.hip's
 //                  claim word; skipped without d_sel, where no group can be
 //                  named twice), runs the whole-call checks and the decision,
 //                  and looks at data_nil of the unstable entries: the first few
@@ -20,7 +20,7 @@
 //                  where its unstable entries start in d_ents and its status in
 //                  rec[p], and the workgroup's sums (records, groups with
 //                  updates) in partial[].
-//   k_lead_scan    lead_step.hip's: the workgroups' record offsets and the
+//   k_lead_scan    step_common.hip's: the workgroups' record offsets and the
 //                  totals.  The host reads the flag word and the totals here --
 //                  the one decision point (INVAL, NOMEM, the peek).
 //   k_ready_emit   two parts in one launch.  Thread i < n owns selection i: it
@@ -36,15 +36,13 @@
 //                  what no owner writes: rec[], partial[], d_ents and the const
 //                  arrays.  <false> is the peek: results alone.
 //
-// Included by ewal_api.hip after lead_step.hip (the claim word, the head
-// words, k_lead_scan, the block scan) and log_append.hip (the block sums).
+// Uses step_common.hip.
 #include "ewal_device.h"
 #include "ewal_internal.h"
 #include "ready_step.h"
 
 namespace rs = ready_step;
 
-#define EREADY_ERR_INVAL 1u
 #define EREADY_LANE_SCAN 4u          // unstable entries a lane looks at by itself
 
 struct EreadyRec {                   // 32 bytes per selection
@@ -133,22 +131,20 @@ __global__ __launch_bounds__(256) void k_ready_count(const EreadyArgs a) {
   rs::Out o;
   uint64_t efirst = 0;
   bool decided = false;
-  if (valid && g >= a.G) err = EREADY_ERR_INVAL;
+  if (valid && g >= a.G) err = STEP_ERR_INVAL;
   if (valid && !err) {
     const uint64_t reserved = eready_load<true>(a, g, in, &efirst);
     // the group's claim: a second selection of the group finds the word taken
-    if (a.sel && atomicMin(a.claim + g, (uint32_t)i) != ELEAD_NOCLAIM) err = EREADY_ERR_INVAL;
-    if (reserved != 0 || in.state > 2 || in.pstate > 2 || in.soft_dirty > 1) err = EREADY_ERR_INVAL;
-    if (in.nlog > a.n_ents_total || efirst > a.n_ents_total - in.nlog) err = EREADY_ERR_INVAL;
+    if (a.sel && !step_claim(a.claim, g, i)) err = STEP_ERR_INVAL;
+    if (reserved != 0 || in.state > 2 || in.pstate > 2 || in.soft_dirty > 1) err = STEP_ERR_INVAL;
+    if (in.nlog > a.n_ents_total || efirst > a.n_ents_total - in.nlog) err = STEP_ERR_INVAL;
     if (!err) {
       o = rs::decide(in);
       if (o.status != lp::ST_OK) eready_void(o, o.status, in);
       decided = true;
     }
   }
-  if (__ballot(err != 0)) {
-    if (err) atomicOr(&a.head->errflag, err);
-  }
+  step_flag(a.head, err);
   // data_nil == 2 among the unstable entries: their bytes are not in d_data
   const uint64_t scan_first = decided ? efirst + o.ents_pos : 0, scan_n = decided ? o.n_ents : 0;
   bool outside = false;
@@ -165,14 +161,14 @@ __global__ __launch_bounds__(256) void k_ready_count(const EreadyArgs a) {
   if (outside) eready_void(o, lp::ST_UNSUPPORTED, in);
   const unsigned long long cnt = decided ? o.n_save : 0;
   unsigned long long total = 0;
-  const unsigned long long loc = elead_block_scan(cnt, &total);
+  const unsigned long long loc = step_block_scan(cnt, &total);
   if (valid) {
     el_v2 *q = (el_v2 *)(a.rec + i);
     const uint64_t status = decided ? (uint64_t)(uint32_t)o.status : 0;
     q[0] = el_v2{cnt, loc};
     q[1] = el_v2{scan_first, status | ((decided && (o.flags & rs::HARD)) ? 1ull << 32 : 0ull)};
   }
-  elog_block_sums(cnt, (decided && (o.flags & rs::UPDATES)) ? 1 : 0, a.partial, blockIdx.x);
+  step_block_sums(cnt, (decided && (o.flags & rs::UPDATES)) ? 1 : 0, a.partial, blockIdx.x);
 }
 
 // the last k in [0, m) with at(k) <= x; at(0) <= x is the caller's

@@ -22,7 +22,7 @@
 //                 msgVoteResp records need against ents_cap (NOMEM), the
 //                 workgroup's sums of messages and of WON records into
 //                 partial[].
-//   k_lead_scan   lead_step.hip's: the workgroups' message offsets and the
+//   k_lead_scan   step_common.hip's: the workgroups' message offsets and the
 //                 totals.  The host reads the flag word and the totals here --
 //                 the one decision point (INVAL, NOMEM, the size query).
 //   k_vote_apply  one lane per record again: a workgroup-wide exclusive scan of
@@ -40,16 +40,10 @@
 // appends at most one entry per record, so the runs' ranges are disjoint), and
 // read every older entry from d_ents.
 //
-// Included by ewal_api.hip after lead_step.hip and lead_prop.hip, whose group
-// loader and checks, message sink, claim word and block scans it uses.
+// Uses step_common.hip, and lead_prop.hip's group loader, checks and message sink.
 #include "ewal_device.h"
 #include "ewal_internal.h"
 #include "vote_step.h"
-
-namespace vs = vote_step;
-
-#define EVOTE_ERR_INVAL 1u
-#define EVOTE_ERR_NOMEM 2u
 
 struct EvoteArgs {
   EpropArgs p;                      // groups, state, G, snaps, ents, n_ents_total, msgs, claim, partial, head
@@ -66,30 +60,23 @@ struct EvoteRec {
   uint64_t group, kind, from, term, index, log_term, rj, pad2;
 };
 
-// The wave's 64 records (4 KiB) as four coalesced 16-B loads per lane,
-// transposed through the wave's 4 KiB of LDS (as log_append.hip's load_app).
+__device__ __forceinline__ EvoteRec evote_unpack(const el_v2 (&u)[4]) {
+  return EvoteRec{u[0].x, u[0].y, u[1].x, u[1].y, u[2].x, u[2].y, u[3].x, u[3].y};
+}
+
+// the wave's 64 records: lane l gets record r0 + l
 __device__ __forceinline__ EvoteRec evote_load_wave(const evote_msg *__restrict__ in, uint64_t n, el_v2 *s_wave,
                                                     uint64_t r0, uint32_t lane) {
-  const el_v2 *src = (const el_v2 *)(in + r0);
-  const uint64_t left = r0 < n ? (n - r0 < 64 ? n - r0 : 64) * 4 : 0;   // 16-B units of this wave
-  el_v2 x[4];
-#pragma unroll
-  for (uint32_t k = 0; k < 4; ++k) {
-    const uint32_t i = k * 64 + lane;
-    x[k] = i < left ? src[i] : el_v2{0, 0};
-  }
-#pragma unroll
-  for (uint32_t k = 0; k < 4; ++k) s_wave[k * 64 + lane] = x[k];
-  __syncthreads();
-  const el_v2 a = s_wave[lane * 4], b = s_wave[lane * 4 + 1], c = s_wave[lane * 4 + 2], d = s_wave[lane * 4 + 3];
-  return EvoteRec{a.x, a.y, b.x, b.y, c.x, c.y, d.x, d.y};
+  el_v2 u[4];
+  step_load_wave(in, n, s_wave, r0, lane, u);
+  return evote_unpack(u);
 }
 
 // One record at an arbitrary place (a run's later records).
 __device__ __forceinline__ EvoteRec evote_load_rec(const evote_msg *p) {
-  const el_v2 *src = (const el_v2 *)p;
-  const el_v2 a = src[0], b = src[1], c = src[2], d = src[3];
-  return EvoteRec{a.x, a.y, b.x, b.y, c.x, c.y, d.x, d.y};
+  el_v2 u[4];
+  step_load_rec(p, u);
+  return evote_unpack(u);
 }
 
 // The group's evote_state; returns the OR of its reserved words.
@@ -109,12 +96,6 @@ __device__ __forceinline__ uint64_t evote_load_state(const evote_state *p, vs::V
 __device__ __forceinline__ bool evote_state_ok(const lp::State &s, const vs::Vote &v, uint64_t reserved) {
   const uint64_t mask = (1ull << (uint32_t)lp::n_slots(s)) - 1;
   return reserved == 0 && v.state <= vs::LEADER && ((v.voted | v.granted) & ~mask) == 0 && (v.granted & ~v.voted) == 0;
-}
-
-__device__ __forceinline__ bool evote_is_head(const EvoteArgs &a, uint64_t i, uint64_t group, uint32_t lane) {
-  uint64_t prev = __shfl_up(group, 1);
-  if (lane == 0 && i > 0 && i < a.n) prev = a.in[i - 1].group;
-  return i < a.n && (i == 0 || prev != group);
 }
 
 // the log as the run sees it: its own entries from scratch, the older ones from d_ents
@@ -215,25 +196,8 @@ __device__ __forceinline__ void evote_run(const EvoteArgs &a, uint64_t i, const 
     if (more) ahead = evote_load_rec(a.in + k + 1);
   }
   if (EMIT) {
-    uint64_t *gw = (uint64_t *)(a.p.groups + g);
-    uint64_t *sw = (uint64_t *)(a.p.state + g);
-    uint64_t *vw = (uint64_t *)(a.vstate + g);
-    if (s.term != s0.term) gw[1] = s.term;
-    if (s.committed != s0.committed) gw[2] = s.committed;
-    if (s.nlog != s0.nlog) gw[4] = s.nlog;
-#pragma unroll
-    for (uint32_t k = 0; k < lp::PEERS; ++k) {
-      if (s.match[k] != s0.match[k]) gw[14 + k] = s.match[k];
-      if (s.next[k] != s0.next[k]) gw[21 + k] = s.next[k];
-    }
-    if (s.unstable != s0.unstable) sw[1] = s.unstable;
-    if (s.pending != s0.pending) sw[2] = s.pending;
-    if (v.state != v0.state) vw[0] = v.state;
-    if (v.vote != v0.vote) vw[1] = v.vote;
-    if (v.lead != v0.lead) vw[2] = v.lead;
-    if (v.elapsed != v0.elapsed) vw[3] = v.elapsed;
-    if (v.voted != v0.voted) vw[4] = v.voted;
-    if (v.granted != v0.granted) vw[5] = v.granted;
+    lp_store_changed(a.p.groups, a.p.state, g, s0, s);
+    vs_store_changed(a.vstate, g, v0, v);
   }
 }
 
@@ -249,18 +213,16 @@ __device__ __forceinline__ uint64_t evote_load_group(const EvoteArgs &a, uint64_
 
 __global__ __launch_bounds__(256) void k_vote_count(const EvoteArgs a) {
   __shared__ el_v2 s_rec[4][256];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint64_t r0 = (uint64_t)blockIdx.x * 256 + wave * 64;
-  const uint64_t i = r0 + lane;
+  const auto [lane, wave, r0, i] = step_lane();
   const EvoteRec r = evote_load_wave(a.in, a.n, s_rec[wave], r0, lane);
   const bool valid = i < a.n;
-  const bool head = evote_is_head(a, i, r.group, lane);
+  const bool head = step_is_head(a.in, a.n, i, r.group, lane);
   uint32_t err = 0;
   unsigned long long tot = 0, nwon = 0;
   if (valid) {
-    if (r.group >= a.p.G) err = EVOTE_ERR_INVAL;
-    if (r.kind != vs::KIND_HUP && r.kind != vs::KIND_VOTE && r.kind != vs::KIND_VOTE_RESP) err = EVOTE_ERR_INVAL;
-    if (r.rj > 1 || r.pad2 != 0) err = EVOTE_ERR_INVAL;   // reject not 0 or 1, or the padding not 0
+    if (r.group >= a.p.G) err = STEP_ERR_INVAL;
+    if (r.kind != vs::KIND_HUP && r.kind != vs::KIND_VOTE && r.kind != vs::KIND_VOTE_RESP) err = STEP_ERR_INVAL;
+    if (r.rj > 1 || r.pad2 != 0) err = STEP_ERR_INVAL;   // reject not 0 or 1, or the padding not 0
   }
   if (head && r.group < a.p.G) {
     lp::State s;
@@ -268,31 +230,27 @@ __global__ __launch_bounds__(256) void k_vote_count(const EvoteArgs a) {
     uint64_t cap = 0, vreserved = 0;
     const uint64_t reserved = evote_load_group(a, r.group, s, v, &cap, &vreserved);
     // the group's claim: the head of a second run finds the word taken
-    if (atomicMin(a.p.claim + r.group, (uint32_t)i) != ELEAD_NOCLAIM) err = EVOTE_ERR_INVAL;
-    if (!eprop_group_ok(a.p, s, cap, reserved) || !evote_state_ok(s, v, vreserved)) err = EVOTE_ERR_INVAL;
+    if (!step_claim(a.p.claim, r.group, i)) err = STEP_ERR_INVAL;
+    if (!eprop_group_ok(a.p, s, cap, reserved) || !evote_state_ok(s, v, vreserved)) err = STEP_ERR_INVAL;
     if (!err) {
       uint64_t nroom = 0;
       evote_run<false>(a, i, r, s, v, false, 0, tot, nwon, nroom);
-      if (cap - s.nlog < nroom) err = EVOTE_ERR_NOMEM;
+      if (cap - s.nlog < nroom) err = STEP_ERR_NOMEM;
     }
   }
-  if (__ballot(err != 0)) {
-    if (err) atomicOr(&a.p.head->errflag, err);
-  }
+  step_flag(a.p.head, err);
   if (valid) a.run_msgs[i] = tot;
-  elog_block_sums(tot, nwon, a.p.partial, blockIdx.x);
+  step_block_sums(tot, nwon, a.p.partial, blockIdx.x);
 }
 
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_vote_apply(const EvoteArgs a) {
   __shared__ el_v2 s_rec[4][256];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint64_t r0 = (uint64_t)blockIdx.x * 256 + wave * 64;
-  const uint64_t i = r0 + lane;
+  const auto [lane, wave, r0, i] = step_lane();
   const EvoteRec r = evote_load_wave(a.in, a.n, s_rec[wave], r0, lane);
-  const bool head = evote_is_head(a, i, r.group, lane);
+  const bool head = step_is_head(a.in, a.n, i, r.group, lane);
   unsigned long long total = 0;
-  const unsigned long long before = elead_block_scan(i < a.n ? a.run_msgs[i] : 0, &total);
+  const unsigned long long before = step_block_scan(i < a.n ? a.run_msgs[i] : 0, &total);
   if (head) {
     lp::State s;
     vs::Vote v;
