@@ -1113,7 +1113,11 @@ typedef struct evote_result {       /* 48 bytes; a DEVICE array of n */
  * *n_msgs).  removed[] / msgDenied routing (raft.go:376-387) and the deferred
  * r.Commit copy stay the caller's.
  * Per record, in Go's order:
- *   kind 0 (msgHup) runs campaign() first (below).
+ *   kind 0 (msgHup) runs campaign() first (below).  A msgHup is a local
+ *     message: raft builds it with Term 0 (raft.go:296) and node.Step drops one
+ *     that arrives over the network (node.go:281-284), so the record's from,
+ *     term, index and log_term are not read and the term switch below is the
+ *     m.Term == 0 case whatever they hold.
  *   The term switch: m.Term == 0 is a local message; m.Term > r.Term runs
  *     becomeFollower(m.Term, lead) with lead = None for a msgVote and m.From
  *     for a msgVoteResp (Go's quirk, kept) and sets flags bit 0; m.Term <
