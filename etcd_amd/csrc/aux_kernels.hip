@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void k_snap(const uint8_t *__restrict__ buf, c
   if (st == 0) {
     // crc32.Update(0, crcTable, Data) = S_n(~0 ^ P(s)) ^ P(e) ^ ~0
     if (a2.split) {   // Data = the concatenation of its segments (snap.pb.go append)
-      const uint32_t lin = bytes_field_lin(buf + d.off, (int64_t)d.len, 2, d.off, buf, pwave, v, s_t4, s_svp, g_shift);
+      const uint32_t lin = bytes_field_lin(buf + d.off, (int64_t)d.len, 2, 0x6u, d.off, buf, pwave, v, s_t4, s_svp, g_shift);
       d.computed = gshift_n(g_shift, d.dlen, 0xffffffffu) ^ lin ^ 0xffffffffu;
     } else if (d.dlen == 0) {
       d.computed = 0;

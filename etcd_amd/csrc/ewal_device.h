@@ -300,10 +300,25 @@ __device__ inline int pb_walk(const P &p, int64_t l, PbField &f1, PbField &f2, P
   return 0;
 }
 
+// Where proto.Skip starts when a second walk steps over the field whose tag
+// is bytes [tag, i) with value wire, so that it frames what follows as
+// pb_walk did.  A known field (bit fn of known) spans its whole tag and what
+// Unmarshal read after it, which is what Skip measures from the tag.  An
+// unknown one is Unmarshal's default arm: Skip(data[i - sizeOfWire:]), with
+// sizeOfWire taken from the tag's VALUE -- after a padded tag that is inside
+// the tag, and the bytes before it belong to no field.
+__device__ __forceinline__ int64_t pb_skip_from(int64_t tag, int64_t i, uint64_t wire, uint32_t known) {
+  const uint32_t fn = (uint32_t)(wire >> 3);
+  if (fn < 32 && ((known >> fn) & 1)) return tag;
+  int64_t sow = 0;
+  do { ++sow; wire >>= 7; } while (wire);
+  return i - sow;
+}
+
 // Every occurrence of field fnum that pb_walk consumed over the same bytes,
 // in order: f(true, off, len) for a non-empty bytes occurrence, f(false,
 // value, 0) for a varint one.  Other fields are stepped over by proto.Skip
-// from their tag; kvar / kbytes (bit fn) name the message's varint / bytes
+// (pb_skip_from); kvar / kbytes (bit fn) name the message's varint / bytes
 // fields, so a known field with the wrong wire type ends the walk where
 // Unmarshal's ErrWrongType does (a message whose error is discarded keeps
 // what came before it).
@@ -332,8 +347,14 @@ __device__ void pb_each(const uint8_t *p, int64_t l, uint32_t fnum, uint32_t kva
       i = post;
       continue;
     }
+    const int64_t at = pb_skip_from(tag, i, wire, kvar | kbytes);
     int64_t sk;
-    if (pb_skip(p + tag, l - tag, sk) || sk <= 0) return;
-    i = tag + sk;
+    if (pb_skip(p + at, l - at, sk) || sk <= 0) return;
+    // Skip measures a bytes field by its length prefix alone: past the end
+    // (pb_walk's ErrUnexpectedEOF) or wrapped below at (its bounds panic)
+    // is where the walk stopped -- i must never leave [0, l]
+    const int64_t hi = (int64_t)((uint64_t)at + (uint64_t)sk);
+    if (hi > l || hi < at) return;
+    i = hi;
   }
 }

@@ -1694,15 +1694,17 @@ __device__ __forceinline__ uint32_t prefix_finish_near_vh(const PrefixNearVH &in
 // repeats), the message read at stream offset base:
 //   lin(A || B) = S_|B|(lin A) ^ lin B,  lin[s, e) = S_{e-s}(P(s)) ^ P(e).
 // Every other field is stepped over as proto.Skip would (its extent is the
-// one the walker consumed).  Rare: split fields only.
+// one the walker consumed: pb_skip_from; known = the message's field set, bit
+// fn).  Rare: split fields only.
 template <class P>
-__device__ uint32_t bytes_field_lin(const P &p, int64_t l, uint32_t fnum, uint64_t base, const uint8_t *__restrict__ buf,
+__device__ uint32_t bytes_field_lin(const P &p, int64_t l, uint32_t fnum, uint32_t known, uint64_t base,
+                                    const uint8_t *__restrict__ buf,
                                     const uint32_t *__restrict__ pwave, const uint32_t *__restrict__ v,
                                     const uint32_t *t4, const uint32_t *svp, const uint32_t *__restrict__ g_shift) {
   int64_t i = 0;
   uint32_t lin = 0;
   while (i < l) {
-    const int64_t at = i;
+    const int64_t tag = i;
     uint64_t wire = 0;
     if (rd_varint(p, i, l, wire, 64)) break;
     if ((uint32_t)(wire >> 3) == fnum && (wire & 7) == 2) {
@@ -1717,6 +1719,7 @@ __device__ uint32_t bytes_field_lin(const P &p, int64_t l, uint32_t fnum, uint64
       i = post;
       continue;
     }
+    const int64_t at = pb_skip_from(tag, i, wire, known);
     int64_t skippy = 0;
     if (pb_skip(gptr(p) + at, l - at, skippy) || skippy <= 0) break;
     i = at + skippy;
@@ -1848,7 +1851,7 @@ __device__ __forceinline__ void decode_general(const uint8_t *__restrict__ buf, 
     // S_n(seed ^ ~0 ^ P(s)) ^ P(e) ^ ~0 with P(s) := 0, P(e) := lin(D)
     pfo[r] = prefix_at(p, pwave, v, buf, s_t4, s_svp);
     pfd[r] = 0;
-    d.chained = bytes_field_lin(R + 8, L, 3, p + 8, buf, pwave, v, s_t4, s_svp, g_shift);
+    d.chained = bytes_field_lin(R + 8, L, 3, 0xeu, p + 8, buf, pwave, v, s_t4, s_svp, g_shift);
     // Go's Data is the concatenation (`m.Data = append(m.Data, ...)`,
     // record.pb.go:112): gathered into the side arena, and the metadata /
     // Entry / HardState decoded from it there
@@ -1970,7 +1973,7 @@ __device__ bool walk_passes(const uint8_t *__restrict__ buf, uint64_t x, int64_t
   uint32_t computed = seed;
   const uint32_t *svp = g_shift + EW_VLOG * 1024;
   if (a3.split) {   // Data = the concatenation of its segments
-    const uint32_t lin = bytes_field_lin(rb, L, 3, x + 8, buf, pwave, v, g_slice, svp, g_shift);
+    const uint32_t lin = bytes_field_lin(rb, L, 3, 0xeu, x + 8, buf, pwave, v, g_slice, svp, g_shift);
     computed = gshift_n(g_shift, (uint64_t)a3.blen, seed ^ 0xffffffffu) ^ lin ^ 0xffffffffu;
   } else if (a3.blen > 0) {
     const uint64_t s = x + 8 + (uint64_t)a3.boff, e = s + (uint64_t)a3.blen;

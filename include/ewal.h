@@ -54,7 +54,14 @@ enum {
   EWAL_PANIC_COMPACT_APPLIED = 45, /* panic("raft: compact index (%d) exceeds applied index (%d)"), raft/raft.go:523-525 */
   EWAL_PANIC_COMPACT_BOUNDS = 46,  /* panic("compact %d out of bounds [%d:%d]"), raft/log.go:162-164 */
   EWAL_UNSUPPORTED_ENCODING = 48,  /* protobuf groups nested deeper than the device
-                                      walker's stack; reported, never guessed */
+                                      walker's stack; reported, never guessed.  An
+                                      unknown group may hold groups 16 deep (17
+                                      start-group tags nested) and every call is still
+                                      exact; with 18 nested, bytes Go accepts get this
+                                      status: ReadAll stops at that frame (fail_record /
+                                      fail_offset name it, in a batch for that shard
+                                      alone), esnap_verify_packed gives it as the file's
+                                      status, emsg_decode_batch_device as the message's */
   /* infrastructure (negative) */
   EWAL_E_HIP = -1,
   EWAL_E_INVAL = -2,
@@ -568,7 +575,10 @@ uint32_t ewal_crc32_combine(uint32_t poly, uint32_t crc_a, uint32_t crc_b, uint6
 /* ---- snapshots: snap.loadSnap / Snapshotter.Load, snap/snapshotter.go:62-111 */
 /* Batch-verify snapshot FILES (snappb.Snapshot envelopes) resident in one
  * device buffer at offs[i], lens[i].  status[i] = EWAL_OK / EWAL_ERR_SNAP_CRC /
- * unmarshal class; crc outputs are the stored and recomputed CRCs.  d_buf
+ * unmarshal class; crc outputs are the stored and recomputed CRCs.  A file
+ * whose snappb.Snapshot or raftpb.Snapshot holds unknown groups nested deeper
+ * than the device walker's stack gets EWAL_UNSUPPORTED_ENCODING (Go loads it);
+ * its status alone is meaningful then.  d_buf
  * must be 16-byte aligned (EWAL_E_INVAL otherwise); offs[i] may be any byte. */
 int esnap_verify_packed(ewal_ctx *ctx, const void *d_buf, uint64_t buf_len, const uint64_t *offs,
                         const uint64_t *lens, uint32_t n, uint32_t poly, int32_t *status,
