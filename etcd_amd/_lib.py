@@ -238,6 +238,15 @@ COMPACT_AT_APPLIED = 1
 COMPACT_PEEK = 1
 COMPACT_NOT_STEPPED, COMPACT_NOT_DUE, COMPACT_COMPACTED, COMPACT_PANICKED = range(4)
 
+
+class TickResult(C.Structure):   # etick_result
+    _fields_ = [("status", C.c_int32), ("action", C.c_int32), ("elapsed", C.c_uint64), ("out_pos", C.c_uint64),
+                ("draw", C.c_uint64)]
+
+
+# etick_result.action
+TICK_IDLE, TICK_HELD, TICK_HUP, TICK_BEAT, TICK_NOT_PROMOTABLE, TICK_PANICKED = range(1, 7)
+
 SNAP_FIELD_DATA, SNAP_FIELD_UNREC, SNAP_FIELD_NODES, SNAP_FIELD_REMOVED = range(4)
 SEG_UNREC, SEG_ENTRY_UNREC, SEG_ENTRY_DATA, SEG_SNAP_UNREC, SEG_SNAP_DATA, SEG_SNAP_NODE, SEG_SNAP_REMOVED = range(7)
 
@@ -472,6 +481,10 @@ _SIGS = {
                                         C.c_uint64, vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "ecompact_req_size": (C.c_uint32, []),
     "ecompact_result_size": (C.c_uint32, []),
+    "etick_batch_device": (C.c_int, [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int64, C.c_int64, vp, C.c_uint64, vp,
+                                     vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "etick_draw": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "etick_result_size": (C.c_uint32, []),
 }
 for _name, (_res, _args) in _SIGS.items():
     if os.environ.get("EWAL_LIB_PATH") and not hasattr(lib, _name):
@@ -503,7 +516,7 @@ def header_symbols(path=HEADER):
     """Every function declared in include/ewal.h."""
     txt = open(path).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead|vote|ready|follow|compact)_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead|vote|ready|follow|compact|tick)_[a-z0-9_]+)\s*\(", txt)))
 
 
 def status_string(st):

@@ -40,6 +40,7 @@
 #include "ready_step.hip"
 #include "follow_step.hip"
 #include "compact_step.hip"
+#include "tick_step.hip"
 #include "ewal_stage.h"
 #include "ewal_wire.h"
 

@@ -548,3 +548,71 @@ int ecompact_batch_device(ewal_ctx *c, elead_group *d_groups, elead_prop_state *
   return EWAL_OK;
 }
 
+uint32_t etick_result_size(void) { return sizeof(etick_result); }
+uint64_t etick_draw(uint64_t seed, uint64_t id, uint64_t term, uint64_t elapsed) {
+  return tick_step::draw(seed, id, term, elapsed);
+}
+
+static_assert(sizeof(etick_result) == 32 && sizeof(EtickRec) == 32 && offsetof(etick_result, elapsed) == 8 &&
+                  offsetof(etick_result, draw) == 24 && offsetof(elead_group, match) == 112 &&
+                  offsetof(elead_group, n_peers) == 48 && offsetof(evote_state, elapsed) == 24 &&
+                  offsetof(evote_msg, from) == 16 && sizeof(elead_local) == 48,
+              "etick layout");
+int etick_batch_device(ewal_ctx *c, const elead_group *d_groups, evote_state *d_vstate, uint64_t G,
+                       const uint64_t *d_sel, uint64_t n, int64_t election, int64_t heartbeat, const uint64_t *d_draws,
+                       uint64_t seed, etick_result *d_res, evote_msg *d_hups, uint64_t hups_cap, elead_local *d_beats,
+                       uint64_t beats_cap, uint64_t *n_hups, uint64_t *n_beats) {
+  if (n_hups) *n_hups = 0;
+  if (n_beats) *n_beats = 0;
+  if (!step_args_ok(c, n, G)) return EWAL_E_INVAL;
+  if (!d_sel && n != G) return EWAL_E_INVAL;
+  if ((d_hups == nullptr) != (d_beats == nullptr)) return EWAL_E_INVAL;
+  if (election < 1 || election > 0x7fffffffll || heartbeat < 0 || heartbeat > 0x7fffffffll) return EWAL_E_INVAL;
+  if (n == 0) return EWAL_OK;
+  if (!d_groups || !d_vstate || !d_res) return EWAL_E_INVAL;
+  if (!aligned(15, {d_groups, d_vstate, d_res, d_hups, d_beats}) || !aligned(7, {d_sel, d_draws})) return EWAL_E_INVAL;
+  // scratch: head | msgBeat head | claim[G] (with d_sel) | rec[n] | hpart[2 * workgroups] | bpart[2 * workgroups]
+  const uint32_t blocks = grid_for(n, 256);
+  Carve cv;
+  cv.add(STEP_HEAD_SLOT);
+  const size_t o_bhead = cv.add(STEP_HEAD_SLOT), o_claim = cv.add(d_sel ? (size_t)G * 4 : 0),
+               o_rec = cv.add((size_t)n * sizeof(EtickRec)), o_hpart = cv.add((size_t)blocks * 16),
+               o_bpart = cv.add((size_t)blocks * 16);
+  if (int st = step_begin(c, cv.size(), 2 * STEP_HEAD_SLOT, d_sel ? o_claim : 0, G)) return st;
+  uint8_t *base = c->lstep.as<uint8_t>();
+  EtickArgs a{};
+  a.groups = d_groups;
+  a.vstate = d_vstate;
+  a.G = G;
+  a.sel = d_sel;
+  a.n = n;
+  a.election = election;
+  a.heartbeat = heartbeat;
+  a.draws = d_draws;
+  a.seed = seed;
+  a.res = d_res;
+  a.hups = d_hups;
+  a.beats = d_beats;
+  a.claim = (uint32_t *)(base + o_claim);
+  a.rec = (EtickRec *)(base + o_rec);
+  a.hpart = (unsigned long long *)(base + o_hpart);
+  a.bpart = (unsigned long long *)(base + o_bpart);
+  a.head = (EleadHead *)base;
+  a.bhead = (EleadHead *)(base + o_bhead);
+  hipLaunchKernelGGL(k_tick_count, dim3(blocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.hpart, blocks, a.head);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.bpart, blocks, a.bhead);
+  EleadHead h;                                       // n_msgs: the msgHup, n_committed: the msgBeat
+  if (int st = step_decide(c, base, 1, &h)) return st;
+  const bool emit = d_hups != nullptr;
+  if (int st = step_status(h, emit, h.n_msgs, hups_cap)) return st;
+  if (int st = step_status(h, emit, h.n_committed, beats_cap)) return st;
+  if (emit)
+    hipLaunchKernelGGL(k_tick_apply<true>, dim3(blocks), dim3(256), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(k_tick_apply<false>, dim3(blocks), dim3(256), 0, c->stream, a);
+  if (int st = step_end(c)) return st;
+  if (n_hups) *n_hups = h.n_msgs;
+  if (n_beats) *n_beats = h.n_committed;
+  return EWAL_OK;
+}

@@ -957,7 +957,7 @@ uint32_t elead_result_size(void);
  * (:279-285) with raftLog.append (raft/log.go:71-75), progress.update
  * (:71-74) and maybeCommit (:248-258), then bcastAppend (:229-236); and
  * bcastHeartbeat / sendHeartbeat (:219-226, :238-246).  Client proposals and
- * heartbeat ticks come in; the grown log (d_ents is WRITTEN here, and only
+ * heartbeat ticks (etick_batch_device's d_beats, below, as they lie) come in; the grown log (d_ents is WRITTEN here, and only
  * here), progress, commit and the fan-out's emsg_out records come out.  The
  * groups are elead_step_batch_device's elead_group records, unchanged, so the
  * same array feeds both calls; what a proposal needs beyond them lives in a
@@ -1083,7 +1083,7 @@ typedef struct evote_state {        /* 64 bytes; a DEVICE array of G, updated in
   uint64_t state;                   /* raft.state: 0 follower, 1 candidate, 2 leader (Go's StateType) */
   uint64_t vote;                    /* HardState.Vote */
   uint64_t lead;                    /* raft.lead */
-  uint64_t elapsed;                 /* raft.elapsed */
+  uint64_t elapsed;                 /* raft.elapsed: Go's int as its bits; etick_batch_device counts it */
   uint64_t voted;                   /* bit s: r.votes has the key peer_id[s] */
   uint64_t granted;                 /* bit s: that value is true (a subset of voted) */
   uint64_t reserved[2];             /* 0 */
@@ -1123,7 +1123,8 @@ typedef struct evote_result {       /* 48 bytes; a DEVICE array of n */
  * *n_msgs).  removed[] / msgDenied routing (raft.go:376-387) and the deferred
  * r.Commit copy stay the caller's.
  * Per record, in Go's order:
- *   kind 0 (msgHup) runs campaign() first (below).  A msgHup is a local
+ *   kind 0 (msgHup) runs campaign() first (below); tickElection's come from
+ *     etick_batch_device's d_hups (below) as they lie.  A msgHup is a local
  *     message: raft builds it with Term 0 (raft.go:296) and node.Step drops one
  *     that arrives over the network (node.go:281-284), so the record's from,
  *     term, index and log_term are not read and the term switch below is the
@@ -1600,6 +1601,100 @@ int ecompact_batch_device(ewal_ctx *ctx, elead_group *d_groups, elead_prop_state
 /* For bindings / tests: the sizes of the two records. */
 uint32_t ecompact_req_size(void);
 uint32_t ecompact_result_size(void);
+
+/* ---- Tick: node.Tick() (raft/node.go:237-238, 262-269), that is r.tick():
+ * tickElection at a follower or a candidate, tickHeartbeat at a leader
+ * (raft/raft.go:287-307, set in becomeFollower / becomeCandidate / becomeLeader,
+ * :309-349), with promotable (:590-595) and isElectionTimeout (:608-617).
+ * Batched over n selected groups of G -- the timer that starts every other
+ * step: it keeps evote_state.elapsed, which the step calls only ever reset, and
+ * it alone produces the msgHup that evote_step_batch_device and the msgBeat that
+ * elead_local_batch_device consume (etcdserver/server.go:255 fires it for every
+ * group on every interval).  A group is its elead_group (read only: id, term,
+ * n_peers, peer_id[]) and its evote_state.  All elapsed arithmetic is Go's int:
+ * int64 that wraps, compared signed; evote_state.elapsed holds the
+ * two's-complement bits. */
+enum { ETICK_IDLE = 1,              /* elapsed incremented, no timeout test passed, no draw */
+       ETICK_HELD = 2,              /* tickElection: d >= 0, a draw was consumed, no timeout */
+       ETICK_HUP = 3,               /* tickElection fired: elapsed = 0, one msgHup */
+       ETICK_BEAT = 4,              /* tickHeartbeat fired: elapsed = 0, one msgBeat */
+       ETICK_NOT_PROMOTABLE = 5,    /* tickElection at a node not among its own peers: elapsed = 0 */
+       ETICK_PANICKED = 6 };        /* the group is unsupported (n_peers > 7) */
+typedef struct etick_result {       /* 32 bytes; a DEVICE array of n */
+  int32_t status, action;           /* EWAL_OK or EWAL_UNSUPPORTED_ENCODING; ETICK_* */
+  uint64_t elapsed;                 /* raft.elapsed after this tick */
+  uint64_t out_pos;                 /* HUP: its index in d_hups; BEAT: in d_beats; else 0 */
+  uint64_t draw;                    /* the rand.Int() value consumed (HELD, HUP), else 0 */
+} etick_result;
+/* Selection i is group d_sel[i], or group i when d_sel == NULL (then n == G),
+ * as in eready_batch_device.  election and heartbeat are raft.electionTimeout
+ * and raft.heartbeatTimeout (the server's are 10 and 1, etcdserver/server.go).
+ * Per selected group, in Go's order:
+ *   state == 2 (leader), tickHeartbeat: e = elapsed + 1; e > heartbeat: elapsed
+ *     = 0 and one elead_local {group, kind = 1 (msgBeat), every other field 0},
+ *     ETICK_BEAT; otherwise elapsed = e, ETICK_IDLE.
+ *   state 0 or 1, tickElection: promotable() is "id is among the first n_peers
+ *     peer_id".  Not promotable: elapsed = 0 WITHOUT the increment,
+ *     ETICK_NOT_PROMOTABLE.  Promotable: e = elapsed + 1, d = e - election.
+ *     d < 0: elapsed = e, ETICK_IDLE, and NO draw is consumed.  d >= 0: with r
+ *     the draw, d > r % election: elapsed = 0 and one evote_msg {group, kind = 0
+ *     (msgHup), from = id, every other field 0}, ETICK_HUP; otherwise elapsed =
+ *     e, ETICK_HELD.
+ *   A group with n_peers > 7: EWAL_UNSUPPORTED_ENCODING, ETICK_PANICKED, left as
+ *     it was (d_res[i].elapsed is the unchanged word) -- reported, never guessed.
+ * The draw.  Go takes rand.Int() from the process-wide source that every
+ * node's goroutine shares: which value a group receives is unspecified in the
+ * reference.  As with map order elsewhere, the library fixes a rule.  With
+ * d_draws given, selection i's draw is d_draws[i] (a shim that replays Go's own
+ * stream fills it).  With d_draws == NULL it is etick_draw(seed, id,
+ * group.term, e), e the incremented elapsed:
+ *   x = seed ^ id * 0x9E3779B97F4A7C15 ^ term * 0xBF58476D1CE4E5B9
+ *            ^ elapsed * 0x94D049BB133111EB
+ *   x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27;
+ *   x *= 0x94D049BB133111EB; x ^= x >> 31; return x >> 1
+ * mod 2^64; 63 bits, as rand.Int()'s.  etick_draw(1, 2, 3, 4) ==
+ * 0x5a86a12931d3dfc7.
+ * Output placement.  d_hups and d_beats are dense and ordered by selection
+ * position; *n_hups and *n_beats are their lengths (both nullable); nothing at
+ * or past them is written.  d_hups goes to evote_step_batch_device as it lies
+ * (a group appears once, so its adjacency rule holds), d_beats to
+ * elead_local_batch_device.  The removed[r.id] gate in front of the resulting
+ * Step (raft.go:376-387) stays the caller's, as do the wall clock that says
+ * when to call and, if Go's stream is wanted, filling d_draws.
+ * Written: evote_state.elapsed of selected groups, only where it changed;
+ * d_res; the two outputs.  elead_group is read only (its match[] and next[]
+ * are not even read); no other word of any record is touched.
+ * d_hups == NULL with d_beats == NULL is the peek: d_res and the counters are
+ * filled and nothing else is modified; the draw is a pure function, so the
+ * peek and the call agree.
+ * Checked on the device before anything is modified (then every array is
+ * untouched and the counters are 0):
+ *   EWAL_E_INVAL  a selected group >= G; a group selected twice;
+ *                 evote_state.state > 2; elead_group.reserved or
+ *                 evote_state.reserved not 0; two equal peer_id within the
+ *                 first min(n_peers, 7) slots; a d_draws[i] >= 2^63
+ *   EWAL_E_NOMEM  the msgHup exceed hups_cap or the msgBeat beats_cap (INVAL
+ *                 wins when both occur)
+ * and on the host: EWAL_E_INVAL for a NULL ctx; for d_groups, d_vstate or d_res
+ * NULL while n > 0; for exactly one of d_hups and d_beats NULL; for d_sel ==
+ * NULL with n != G; for d_groups, d_vstate, d_res, d_hups, d_beats not 16-byte
+ * aligned or d_sel, d_draws not 8-byte aligned; for n or G >= 2^31 - 1; for
+ * election outside [1, 2^31 - 1] (Go divides by zero at 0; a negative divisor
+ * is not restated) and heartbeat outside [0, 2^31 - 1].  n == 0: EWAL_OK,
+ * counters 0.  A compute call on the ctx's stream; ewal_last_device_ms covers
+ * it; a repeated call of the same or a smaller shape allocates nothing. */
+int etick_batch_device(ewal_ctx *ctx, const elead_group *d_groups, evote_state *d_vstate, uint64_t G,
+                       const uint64_t *d_sel /* n group numbers; NULL: n == G, group i */, uint64_t n,
+                       int64_t election, int64_t heartbeat,
+                       const uint64_t *d_draws /* n, nullable */, uint64_t seed,
+                       etick_result *d_res,
+                       evote_msg *d_hups /* NULL with d_beats NULL: peek */, uint64_t hups_cap,
+                       elead_local *d_beats, uint64_t beats_cap,
+                       uint64_t *n_hups, uint64_t *n_beats);
+/* Host only: the draw rule above (etcd_amd/csrc/tick_step.h). */
+uint64_t etick_draw(uint64_t seed, uint64_t id, uint64_t term, uint64_t elapsed);
+/* For bindings / tests: sizeof(etick_result). */
+uint32_t etick_result_size(void);
 
 /* ---- raft ingress: raftpb.Message.Unmarshal, raft/raftpb/raft.pb.go:407-617
  * (called per POST /raft in etcdserver/etcdhttp/http.go:119-146), batched
