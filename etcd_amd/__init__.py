@@ -14,6 +14,7 @@ Product layout:
   raftfollow.py batched follower step: msgApp / msgSnap (the term switch, maybeAppend, restore, the msgAppResp)
   raftcompact.py batched log compaction: node.Compact (raft.compact, raftLog.snap, the window's slide)
   rafttick.py  batched Tick: tickElection / tickHeartbeat (elapsed, the msgHup and msgBeat that start the steps)
+  raftconf.py  batched membership: ApplyConfChange (addNode / removeNode), the removed[] gate, the ConfChange scan
   crc.py       `pkg/crc` digest (chained CRC-32C) over host or device buffers
   raftmsg.py   batched `raftpb.Message` decode (the /raft ingress) and Marshal (the egress)
   shard.py     per-rank shard assignment, the RCCL summary all-reduce and the
@@ -31,9 +32,13 @@ from .raftready import ready_batch, ready_batch_device  # noqa: F401
 from .raftfollow import follow_batch, follow_batch_device  # noqa: F401
 from .raftcompact import compact_batch, compact_batch_device  # noqa: F401
 from .rafttick import tick_batch, tick_batch_device  # noqa: F401
+from .raftconf import (conf_batch, conf_batch_device, scan_committed, scan_committed_device, gate_batch,  # noqa: F401
+                       gate_batch_device, pack_cstate, unpack_cstate, removed_u64)
 
 __all__ = ["Context", "OpenAtIndex", "Create", "Encoder", "readall_bytes", "synth_wal", "save_packed", "save_dir",
            "snap_name", "append_batch", "append_batch_device", "lead_step_batch", "lead_step_batch_device",
            "local_batch", "local_batch_device", "vote_batch", "vote_batch_device", "ready_batch",
            "ready_batch_device", "follow_batch", "follow_batch_device",
-           "compact_batch", "compact_batch_device", "tick_batch", "tick_batch_device"]
+           "compact_batch", "compact_batch_device", "tick_batch", "tick_batch_device",
+           "conf_batch", "conf_batch_device", "scan_committed", "scan_committed_device", "gate_batch",
+           "gate_batch_device", "pack_cstate", "unpack_cstate", "removed_u64"]

@@ -59,6 +59,7 @@ PANIC_NIL_ENTRY = 43
 PANIC_DOUBLE_CONF = 44
 PANIC_COMPACT_APPLIED = 45
 PANIC_COMPACT_BOUNDS = 46
+PANIC_CONF_TYPE = 47
 UNSUPPORTED_ENCODING = 48
 E_HIP, E_INVAL, E_NOMEM, E_NODEVICE, E_TIMEOUT, E_IO = -1, -2, -3, -4, -5, -6
 
@@ -246,6 +247,42 @@ class TickResult(C.Structure):   # etick_result
 
 # etick_result.action
 TICK_IDLE, TICK_HELD, TICK_HUP, TICK_BEAT, TICK_NOT_PROMOTABLE, TICK_PANICKED = range(1, 7)
+
+
+class ConfState(C.Structure):   # econf_state
+    _fields_ = [("n_removed", C.c_uint64), ("removed", C.c_uint64 * 14), ("reserved", C.c_uint64)]
+
+
+class ConfReq(C.Structure):   # econf_req
+    _fields_ = [("group", C.c_uint64), ("kind", C.c_uint64), ("node", C.c_uint64), ("pad", C.c_uint64)]
+
+
+class ConfResult(C.Structure):   # econf_result
+    _fields_ = [("status", C.c_int32), ("action", C.c_int32), ("msg_first", C.c_uint64), ("n_msgs", C.c_uint64),
+                ("n_peers", C.c_uint64), ("n_removed", C.c_uint64), ("pad", C.c_uint64)]
+
+
+class ConfApplied(C.Structure):   # econf_applied
+    _fields_ = [("id", C.c_uint64), ("index", C.c_uint64), ("term", C.c_uint64), ("ent_pos", C.c_uint64)]
+
+
+class ConfScanResult(C.Structure):   # econf_scan_result
+    _fields_ = [("status", C.c_int32), ("detail", C.c_int32), ("req_first", C.c_uint64), ("n_reqs", C.c_uint64),
+                ("bad_pos", C.c_uint64), ("n_scanned", C.c_uint64), ("pad", C.c_uint64)]
+
+
+class ConfGateResult(C.Structure):   # econf_gate_result
+    _fields_ = [("status", C.c_int32), ("action", C.c_int32), ("pass_pos", C.c_uint64), ("msg_pos", C.c_uint64),
+                ("pad", C.c_uint64)]
+
+
+# econf_req.kind, econf_result.action, econf_gate_result.action, econf_gate_batch_device's from_word
+CONF_ADD, CONF_REMOVE, CONF_DENIED, CONF_RELOAD = 1, 2, 3, 4
+(CONF_NOT_STEPPED, CONF_ADDED, CONF_REMOVED, CONF_DENIED_BACK, CONF_STOPPED, CONF_RELOADED,
+ CONF_PANICKED) = range(7)
+CONF_G_PASS, CONF_G_DENIED, CONF_G_DROPPED = 1, 2, 3
+CONF_FROM_SELF = 0xFFFFFFFF
+CONF_MAX_REMOVED = 14
 
 SNAP_FIELD_DATA, SNAP_FIELD_UNREC, SNAP_FIELD_NODES, SNAP_FIELD_REMOVED = range(4)
 SEG_UNREC, SEG_ENTRY_UNREC, SEG_ENTRY_DATA, SEG_SNAP_UNREC, SEG_SNAP_DATA, SEG_SNAP_NODE, SEG_SNAP_REMOVED = range(7)
@@ -485,6 +522,18 @@ _SIGS = {
                                      vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "etick_draw": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     "etick_result_size": (C.c_uint32, []),
+    "econf_batch_device": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp,
+                                     C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "econf_scan_committed_device": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp,
+                                              vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "econf_gate_batch_device": (C.c_int, [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp,
+                                          C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "econf_state_size": (C.c_uint32, []),
+    "econf_req_size": (C.c_uint32, []),
+    "econf_result_size": (C.c_uint32, []),
+    "econf_applied_size": (C.c_uint32, []),
+    "econf_scan_result_size": (C.c_uint32, []),
+    "econf_gate_result_size": (C.c_uint32, []),
 }
 for _name, (_res, _args) in _SIGS.items():
     if os.environ.get("EWAL_LIB_PATH") and not hasattr(lib, _name):
@@ -516,7 +565,7 @@ def header_symbols(path=HEADER):
     """Every function declared in include/ewal.h."""
     txt = open(path).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead|vote|ready|follow|compact|tick)_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead|vote|ready|follow|compact|tick|conf)_[a-z0-9_]+)\s*\(", txt)))
 
 
 def status_string(st):
@@ -547,6 +596,6 @@ def check(st, detail=0, record=-1, offset=-1):
         return
     if st == E_NODEVICE:
         raise NoDeviceError(st)
-    if 32 <= st <= 46:
+    if 32 <= st <= 47:
         raise GoPanic(st, detail, record, offset)
     raise EwalError(st, detail, record, offset)

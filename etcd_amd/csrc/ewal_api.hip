@@ -41,6 +41,7 @@
 #include "follow_step.hip"
 #include "compact_step.hip"
 #include "tick_step.hip"
+#include "conf_step.hip"
 #include "ewal_stage.h"
 #include "ewal_wire.h"
 
@@ -196,7 +197,8 @@ struct ewal_ctx {
   // calls on a ctx never overlap, and every call writes each region it carves
   // (head words, the groups' claims, per-record words, per-workgroup partial
   // sums) before it reads it; and ecompact_batch_device's overlapping move
-  // class in flight, which is live together with that call's scratch
+  // class in flight, which is live together with that call's scratch (as are
+  // econf_scan_committed_device's per-entry records, sized in mid-call)
   DevBuf lstep, lcompact_stage;
   std::vector<uint64_t> bent_first, bnents;   // per shard: first ent in bents, count
   std::vector<std::vector<ewal_unrec>> bunrec;       // per shard replayed alone: its XXX_unrecognized side list

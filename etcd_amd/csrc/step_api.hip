@@ -616,3 +616,206 @@ int etick_batch_device(ewal_ctx *c, const elead_group *d_groups, evote_state *d_
   if (n_beats) *n_beats = h.n_committed;
   return EWAL_OK;
 }
+
+uint32_t econf_state_size(void) { return sizeof(econf_state); }
+uint32_t econf_req_size(void) { return sizeof(econf_req); }
+uint32_t econf_result_size(void) { return sizeof(econf_result); }
+uint32_t econf_applied_size(void) { return sizeof(econf_applied); }
+uint32_t econf_scan_result_size(void) { return sizeof(econf_scan_result); }
+uint32_t econf_gate_result_size(void) { return sizeof(econf_gate_result); }
+
+static_assert(sizeof(econf_state) == 128 && sizeof(econf_req) == 32 && sizeof(econf_result) == 48 &&
+                  sizeof(econf_applied) == 32 && sizeof(econf_scan_result) == 48 && sizeof(econf_gate_result) == 32 &&
+                  sizeof(EcscanRec) == 48 && sizeof(EgateRec) == 32 && offsetof(econf_state, reserved) == 120 &&
+                  offsetof(econf_result, n_peers) == 24 && offsetof(econf_scan_result, bad_pos) == 24 &&
+                  offsetof(eready_result, committed_first) == 48 && offsetof(eready_state, soft_dirty) == 56 &&
+                  offsetof(elead_snap, removed_off) == 48 && offsetof(elead_prop_state, pending_conf) == 16 &&
+                  sizeof(emsg_out) == 144,
+              "econf layout");
+int econf_batch_device(ewal_ctx *c, elead_group *d_groups, elead_prop_state *d_pstate, evote_state *d_vstate,
+                       eready_state *d_rstate, econf_state *d_cstate, uint64_t G, const elead_snap *d_snaps,
+                       const uint64_t *d_u64, uint64_t n_u64, const econf_req *d_reqs, uint64_t n, econf_result *d_res,
+                       emsg_out *d_msgs, uint64_t msgs_cap, uint64_t *n_msgs, uint64_t *n_changed) {
+  if (n_msgs) *n_msgs = 0;
+  if (n_changed) *n_changed = 0;
+  if (!step_args_ok(c, n, G)) return EWAL_E_INVAL;
+  if (n == 0) return EWAL_OK;
+  if (!d_groups || !d_pstate || !d_vstate || !d_rstate || !d_cstate || !d_reqs || !d_res || (n_u64 && !d_u64))
+    return EWAL_E_INVAL;
+  if (!aligned(15, {d_groups, d_pstate, d_vstate, d_rstate, d_cstate, d_snaps, d_reqs, d_res, d_msgs}) ||
+      !aligned(7, {d_u64}))
+    return EWAL_E_INVAL;
+  // scratch: head | claim[G] | run_msgs[n] | partial[2 * workgroups]
+  const uint32_t blocks = grid_for(n, 256);
+  Carve cv;
+  cv.add(STEP_HEAD_SLOT);
+  const size_t o_claim = cv.add((size_t)G * 4), o_run = cv.add((size_t)n * 8), o_part = cv.add((size_t)blocks * 16);
+  if (int st = step_begin(c, cv.size(), sizeof(EleadHead), o_claim, G)) return st;
+  uint8_t *base = c->lstep.as<uint8_t>();
+  EconfArgs a{};
+  a.groups = d_groups;
+  a.pstate = d_pstate;
+  a.vstate = d_vstate;
+  a.rstate = d_rstate;
+  a.cstate = d_cstate;
+  a.G = G;
+  a.snaps = d_snaps;
+  a.u64 = d_u64;
+  a.n_u64 = n_u64;
+  a.in = d_reqs;
+  a.n = n;
+  a.res = d_res;
+  a.msgs = d_msgs;
+  a.head = (EleadHead *)base;
+  a.claim = (uint32_t *)(base + o_claim);
+  a.run_msgs = (unsigned long long *)(base + o_run);
+  a.partial = (unsigned long long *)(base + o_part);
+  hipLaunchKernelGGL(k_conf_count, dim3(blocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.partial, blocks, a.head);
+  EleadHead h;
+  if (int st = step_decide(c, base, 1, &h)) return st;
+  if (int st = step_status(h, d_msgs, h.n_msgs, msgs_cap)) return st;
+  if (d_msgs)
+    hipLaunchKernelGGL(k_conf_apply<true>, dim3(blocks), dim3(256), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(k_conf_apply<false>, dim3(blocks), dim3(256), 0, c->stream, a);
+  if (int st = step_end(c)) return st;
+  if (n_msgs) *n_msgs = h.n_msgs;
+  if (n_changed) *n_changed = h.n_committed;
+  return EWAL_OK;
+}
+
+int econf_scan_committed_device(ewal_ctx *c, const eready_result *d_ready, const uint64_t *d_sel, uint64_t n,
+                                uint64_t G, const ewal_entry *d_ents, uint64_t n_ents_total, const void *d_data,
+                                uint64_t data_len_total, econf_scan_result *d_scan, econf_req *d_reqs,
+                                econf_applied *d_applied, uint64_t reqs_cap, uint64_t *n_reqs, uint64_t *n_entries) {
+  if (n_reqs) *n_reqs = 0;
+  if (n_entries) *n_entries = 0;
+  if (!step_args_ok(c, n, G) || n_ents_total >= 0x7fffffffull) return EWAL_E_INVAL;
+  if (!d_sel && n != G) return EWAL_E_INVAL;
+  if ((d_reqs == nullptr) != (d_applied == nullptr)) return EWAL_E_INVAL;
+  if (n == 0) return EWAL_OK;
+  if (!d_ready || !d_scan || (n_ents_total && !d_ents) || (data_len_total && !d_data)) return EWAL_E_INVAL;
+  if (!aligned(15, {d_ready, d_scan, d_reqs, d_applied}) || !aligned(7, {d_ents, d_sel})) return EWAL_E_INVAL;
+  // scratch: head | entry head | selbad[n] | selloc[n] | spart[2 * selection workgroups]; the per-entry
+  // records, sized once the entries are counted, live in the ctx's second scratch
+  const uint32_t sblocks = grid_for(n, 256);
+  Carve cv;
+  cv.add(STEP_HEAD_SLOT);
+  const size_t o_ehead = cv.add(STEP_HEAD_SLOT), o_bad = cv.add((size_t)n * 4), o_loc = cv.add((size_t)n * 8),
+               o_spart = cv.add((size_t)sblocks * 16);
+  if (int st = step_begin(c, cv.size(), 2 * STEP_HEAD_SLOT, 0, 0)) return st;
+  uint8_t *base = c->lstep.as<uint8_t>();
+  EcscanArgs a{};
+  a.ready = d_ready;
+  a.sel = d_sel;
+  a.n = n;
+  a.G = G;
+  a.ents = d_ents;
+  a.n_ents_total = n_ents_total;
+  a.data = (const uint8_t *)d_data;
+  a.data_len_total = data_len_total;
+  a.scan = d_scan;
+  a.reqs = d_reqs;
+  a.applied = d_applied;
+  a.head = (EleadHead *)base;
+  a.ehead = (EleadHead *)(base + o_ehead);
+  a.selbad = (uint32_t *)(base + o_bad);
+  a.selloc = (unsigned long long *)(base + o_loc);
+  a.spart = (unsigned long long *)(base + o_spart);
+  hipLaunchKernelGGL(k_cscan_sel, dim3(sblocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.spart, sblocks, a.head);
+  EleadHead h[2];                                    // the committed entries; the requests
+  if (int st = step_decide(c, base, 1, h)) return st;
+  if (int st = step_status(h[0], false, 0, 0)) return st;
+  // each selection's range lies inside d_ents, but ranges may coincide: the lanes are 32-bit ordinals
+  if (h[0].n_msgs >= 0x7fffffffull) return EWAL_E_INVAL;
+  a.T = h[0].n_msgs;
+  const uint32_t eblocks = grid_for(a.T, 256);
+  if (a.T) {
+    Carve ev;
+    const size_t o_rec = ev.add((size_t)a.T * sizeof(EcscanRec)), o_pos = ev.add((size_t)a.T * 8),
+                 o_epart = ev.add((size_t)eblocks * 16);
+    EW_CHECK(c->lcompact_stage.ensure(ev.size()));
+    uint8_t *eb = c->lcompact_stage.as<uint8_t>();
+    a.erec = (EcscanRec *)(eb + o_rec);
+    a.epos = (unsigned long long *)(eb + o_pos);
+    a.epart = (unsigned long long *)(eb + o_epart);
+    hipLaunchKernelGGL(k_cscan_decode, dim3(eblocks), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(k_cscan_count, dim3(eblocks), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.epart, eblocks, a.ehead);
+    // the decision point: the decode's flag word lies in the first head, the requests in the second
+    if (int st = step_decide(c, base, 2, h)) return st;
+    if (int st = step_status(h[0], d_reqs, h[1].n_msgs, reqs_cap)) return st;
+    a.R = h[1].n_msgs;
+    if (d_reqs)
+      hipLaunchKernelGGL(k_cscan_emit<true>, dim3(eblocks), dim3(256), 0, c->stream, a);
+    else
+      hipLaunchKernelGGL(k_cscan_emit<false>, dim3(eblocks), dim3(256), 0, c->stream, a);
+  }
+  hipLaunchKernelGGL(k_cscan_rows, dim3(sblocks), dim3(256), 0, c->stream, a);
+  if (int st = step_end(c)) return st;
+  if (n_reqs) *n_reqs = a.R;
+  if (n_entries) *n_entries = a.T;
+  return EWAL_OK;
+}
+
+int econf_gate_batch_device(ewal_ctx *c, const elead_group *d_groups, const econf_state *d_cstate, uint64_t G,
+                            const void *d_recs, uint64_t n, uint32_t rec_bytes, uint32_t from_word,
+                            econf_gate_result *d_res, void *d_pass, uint64_t pass_cap, emsg_out *d_msgs,
+                            uint64_t msgs_cap, uint64_t *n_pass, uint64_t *n_msgs) {
+  if (n_pass) *n_pass = 0;
+  if (n_msgs) *n_msgs = 0;
+  if (!step_args_ok(c, n, G)) return EWAL_E_INVAL;
+  if (rec_bytes != 48 && rec_bytes != 64 && rec_bytes != 96) return EWAL_E_INVAL;
+  if (from_word != ECONF_FROM_SELF && (from_word < 1 || from_word >= rec_bytes / 8)) return EWAL_E_INVAL;
+  if ((d_pass == nullptr) != (d_msgs == nullptr)) return EWAL_E_INVAL;
+  if (n == 0) return EWAL_OK;
+  if (!d_groups || !d_cstate || !d_recs || !d_res) return EWAL_E_INVAL;
+  if (!aligned(15, {d_groups, d_cstate, d_recs, d_res, d_pass, d_msgs})) return EWAL_E_INVAL;
+  if (d_pass) {
+    const uintptr_t r0 = (uintptr_t)d_recs, r1 = r0 + (uintptr_t)n * rec_bytes, p0 = (uintptr_t)d_pass,
+                    p1 = p0 + (uintptr_t)std::min(pass_cap, n) * rec_bytes;
+    if (r0 < p1 && p0 < r1) return EWAL_E_INVAL;
+  }
+  // scratch: head | message head | rec[n] | ppart[2 * workgroups] | mpart[2 * workgroups]
+  const uint32_t blocks = grid_for(n, 256);
+  Carve cv;
+  cv.add(STEP_HEAD_SLOT);
+  const size_t o_mhead = cv.add(STEP_HEAD_SLOT), o_rec = cv.add((size_t)n * sizeof(EgateRec)),
+               o_ppart = cv.add((size_t)blocks * 16), o_mpart = cv.add((size_t)blocks * 16);
+  if (int st = step_begin(c, cv.size(), 2 * STEP_HEAD_SLOT, 0, 0)) return st;
+  uint8_t *base = c->lstep.as<uint8_t>();
+  EgateArgs a{};
+  a.groups = d_groups;
+  a.cstate = d_cstate;
+  a.G = G;
+  a.recs = (const uint8_t *)d_recs;
+  a.n = n;
+  a.rec_bytes = rec_bytes;
+  a.from_word = from_word;
+  a.res = d_res;
+  a.pass = (uint8_t *)d_pass;
+  a.msgs = d_msgs;
+  a.head = (EleadHead *)base;
+  a.mhead = (EleadHead *)(base + o_mhead);
+  a.rec = (EgateRec *)(base + o_rec);
+  a.ppart = (unsigned long long *)(base + o_ppart);
+  a.mpart = (unsigned long long *)(base + o_mpart);
+  hipLaunchKernelGGL(k_gate_count, dim3(blocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.ppart, blocks, a.head);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.mpart, blocks, a.mhead);
+  EleadHead h;                                       // n_msgs: the copies, n_committed: the messages
+  if (int st = step_decide(c, base, 1, &h)) return st;
+  const bool emit = d_pass != nullptr;
+  if (int st = step_status(h, emit, h.n_msgs, pass_cap)) return st;
+  if (int st = step_status(h, emit, h.n_committed, msgs_cap)) return st;
+  if (emit)
+    hipLaunchKernelGGL(k_gate_apply<true>, dim3(blocks), dim3(256), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(k_gate_apply<false>, dim3(blocks), dim3(256), 0, c->stream, a);
+  if (int st = step_end(c)) return st;
+  if (n_pass) *n_pass = h.n_msgs;
+  if (n_msgs) *n_msgs = h.n_committed;
+  return EWAL_OK;
+}

@@ -53,6 +53,7 @@ enum {
   EWAL_PANIC_DOUBLE_CONF = 44,     /* panic("unexpected double uncommitted config entry"), raft/raft.go:344 */
   EWAL_PANIC_COMPACT_APPLIED = 45, /* panic("raft: compact index (%d) exceeds applied index (%d)"), raft/raft.go:523-525 */
   EWAL_PANIC_COMPACT_BOUNDS = 46,  /* panic("compact %d out of bounds [%d:%d]"), raft/log.go:162-164 */
+  EWAL_PANIC_CONF_TYPE = 47,       /* panic("unexpected conf type"), raft/node.go:235 */
   EWAL_UNSUPPORTED_ENCODING = 48,  /* protobuf groups nested deeper than the device
                                       walker's stack; reported, never guessed.  An
                                       unknown group may hold groups 16 deep (17
@@ -881,7 +882,8 @@ typedef struct elead_result {      /* 48 bytes; a DEVICE array of n */
  *     Every later response of that group in this call is ELEAD_NOT_STEPPED,
  *     has no effect, and is the caller's to step afterwards.
  *   removed[m.From] and msgDenied (raft.go:376-387) are the caller's routing
- *     and are not restated: such messages must not be handed to this call.
+ *     and are not restated: such messages must not be handed to this call
+ *     (econf_gate_batch_device, below, filters d_resps by removed[from]).
  *   reject != 0: maybeDecrTo(index) is false when match != 0 or next - 1 !=
  *     index: ELEAD_STALE, no message.  Otherwise next = next - 1, or 1 when
  *     that is 0: ELEAD_PROBE and one sendAppend(from).
@@ -995,7 +997,8 @@ typedef struct elead_local_result { /* 48 bytes; a DEVICE array of n */
  * before i also when n_msgs == 0, and no emsg_out at or past *n_msgs is
  * written.  *n_appended = the ELEAD_L_APPENDED records (nullable, as *n_msgs).
  * Proposals carry Term == 0 (send, raft.go:190-199), so Step's term switch is
- * "local message"; removed[] / msgDenied routing stays the caller's.
+ * "local message"; removed[] / msgDenied routing stays the caller's
+ * (econf_gate_batch_device with ECONF_FROM_SELF, below).
  * Per record:
  *   kind 1 (msgBeat): one emsg_out per peer slot whose peer_id != id, in slot
  *     order: type = 3 (sendHeartbeat's empty msgApp), to, from = id, term =
@@ -1121,7 +1124,8 @@ typedef struct evote_result {       /* 48 bytes; a DEVICE array of n */
  * the messages of the records before i also when n_msgs == 0, and no emsg_out
  * at or past *n_msgs is written.  *n_won = the EVOTE_WON records (nullable, as
  * *n_msgs).  removed[] / msgDenied routing (raft.go:376-387) and the deferred
- * r.Commit copy stay the caller's.
+ * r.Commit copy stay the caller's (the routing is econf_gate_batch_device's and
+ * econf_batch_device's kind 3, below).
  * Per record, in Go's order:
  *   kind 0 (msgHup) runs campaign() first (below); tickElection's come from
  *     etick_batch_device's d_hups (below) as they lie.  A msgHup is a local
@@ -1270,7 +1274,8 @@ typedef struct eready_result {      /* 96 bytes; a DEVICE array of n */
  *   rd.SoftState (EREADY_SOFT): vstate.lead != lead, vstate.state != state, or
  *     soft_dirty == 1.  SoftState.Nodes and ShouldStop change only through
  *     addNode / removeNode / msgDenied, the caller's on the host: after any of
- *     them it sets soft_dirty.  Go compares Nodes with reflect.DeepEqual over a
+ *     them it sets soft_dirty (econf_batch_device, below, is all three on the
+ *     device and sets it itself).  Go compares Nodes with reflect.DeepEqual over a
  *     slice built in map order, so with two or more peers Go's own answer is
  *     not deterministic; that is NOT reproduced -- the library's order is slot
  *     order, as everywhere else.
@@ -1393,7 +1398,8 @@ typedef struct efollow_result {     /* 96 bytes; a DEVICE array of n */
  * previous one left, the responses are dense and ordered by record, msg_first
  * counts the responses of the records before i also when n_msgs == 0, and no
  * emsg_out at or past *n_msgs is written.  removed[] / msgDenied routing and
- * the deferred r.Commit copy stay the caller's.
+ * the deferred r.Commit copy stay the caller's (the routing is
+ * econf_gate_batch_device's, below).
  * The run rule.  After a record of a run has appended entries (n_app > 0) or
  * restored, a later record of that run that carries entries (n_ents > 0) or is
  * a msgSnap is EFOLLOW_DEFERRED with status EWAL_OK, and so is the rest of the
@@ -1436,7 +1442,8 @@ typedef struct efollow_result {     /* 96 bytes; a DEVICE array of n */
  *     or one of the first n_peers peer_id changed; pending_conf and the votes
  *     are untouched; the response carries index = lastIndex() = s.index.
  *     r.removed from RemovedNodes stays the caller's, as removed[] does
- *     everywhere: EFOLLOW_RESTORED tells it.
+ *     everywhere: EFOLLOW_RESTORED tells it (econf_batch_device's kind 4,
+ *     below, is that half on the device).
  *     The leader's d_snaps[g] that a msgSnap carries has a device-side writer
  *     too: ecompact_batch_device (below).
  * EWAL_UNSUPPORTED_ENCODING, reported, never guessed: the first record of a
@@ -1557,7 +1564,8 @@ typedef struct ecompact_result {    /* 64 bytes; a DEVICE array of n */
  *     snapshot is replaced.  The slots past n_left keep what they held.
  *   raftLog.snap: d_snaps[g] = {index, term, data_off, data_len, nodes_off,
  *     n_nodes, removed_off, n_removed}; r.removedNodes() comes from the request,
- *     as removed[] is the caller's everywhere.  ECOMPACT_COMPACTED.
+ *     as removed[] is the caller's everywhere (the econf_state's ids, below,
+ *     copied into d_u64).  ECOMPACT_COMPACTED.
  * Go assigns the snapshot before raftLog.compact can panic; here a panicking
  * group is left exactly as it was, d_snaps[g] included, as in every other call
  * -- the process in Go is dead at that point.  A panicking or unsupported
@@ -1659,7 +1667,8 @@ typedef struct etick_result {       /* 32 bytes; a DEVICE array of n */
  * or past them is written.  d_hups goes to evote_step_batch_device as it lies
  * (a group appears once, so its adjacency rule holds), d_beats to
  * elead_local_batch_device.  The removed[r.id] gate in front of the resulting
- * Step (raft.go:376-387) stays the caller's, as do the wall clock that says
+ * Step (raft.go:376-387) stays the caller's (econf_gate_batch_device with
+ * ECONF_FROM_SELF over d_hups and d_beats, below), as do the wall clock that says
  * when to call and, if Go's stream is wanted, filling d_draws.
  * Written: evote_state.elapsed of selected groups, only where it changed;
  * d_res; the two outputs.  elead_group is read only (its match[] and next[]
@@ -1695,6 +1704,232 @@ int etick_batch_device(ewal_ctx *ctx, const elead_group *d_groups, evote_state *
 uint64_t etick_draw(uint64_t seed, uint64_t id, uint64_t term, uint64_t elapsed);
 /* For bindings / tests: sizeof(etick_result). */
 uint32_t etick_result_size(void);
+
+/* ---- Membership: node.ApplyConfChange (raft/node.go:228-236, 318-323) with
+ * raft.addNode / removeNode (raft/raft.go:426-435) and setProgress /
+ * delProgress (:582-588); the removed[] / msgDenied lines at the head of
+ * raft.Step (:376-387); the removed half of raft.restore (:549-552); and the
+ * server loop's EntryConfChange arm (etcdserver/server.go:265-286) with
+ * ConfChange.Unmarshal (raft/raftpb/raft.pb.go:705-813).  Three calls on the
+ * records the step calls share, plus one side record: the key set of
+ * r.removed, in insertion order.  StartNode and RestartNode build
+ * newRaft(id, nil, ...): a node gets its peers only by applying the committed
+ * ConfChange entries of its log, so these calls are what lets a restarted host
+ * reach its first election without per-group host work.  All arithmetic is
+ * Go's uint64 and wraps. */
+typedef struct econf_state {        /* 128 bytes; a DEVICE array of G, updated in place */
+  uint64_t n_removed;               /* len(r.removed): 0..14 */
+  uint64_t removed[14];             /* its keys in insertion order; the slots past n_removed are not read */
+  uint64_t reserved;                /* 0 */
+} econf_state;
+typedef struct econf_req {          /* 32 bytes; one request; a DEVICE array of n */
+  uint64_t group;                   /* which group steps it */
+  uint64_t kind;                    /* 1 addNode, 2 removeNode (ConfChange.Type + 1), 3 msgDenied, 4 reload */
+  uint64_t node;                    /* cc.NodeID; kind 3: m.From; kind 4: 0 */
+  uint64_t pad;                     /* 0 */
+} econf_req;
+enum { ECONF_NOT_STEPPED = 0,       /* after a panic in its group's run: the caller's to step */
+       ECONF_ADDED = 1,             /* kind 1 */
+       ECONF_REMOVED = 2,           /* kind 2 */
+       ECONF_DENIED_BACK = 3,       /* kind 3 from a removed node: a msgDenied goes back (none to oneself) */
+       ECONF_STOPPED = 4,           /* kind 3 from a live node: removed[id] = true */
+       ECONF_RELOADED = 5,          /* kind 4 */
+       ECONF_PANICKED = 6 };        /* Go panics (status says where), or the request is unsupported */
+typedef struct econf_result {       /* 48 bytes; a DEVICE array of n */
+  int32_t status, action;           /* EWAL_OK, EWAL_PANIC_CONF_TYPE, EWAL_UNSUPPORTED_ENCODING; ECONF_* */
+  uint64_t msg_first, n_msgs;       /* its messages: d_msgs[msg_first, + n_msgs) */
+  uint64_t n_peers, n_removed;      /* len(r.prs) and len(r.removed) after this request */
+  uint64_t pad;                     /* 0 */
+} econf_result;
+/* econf_batch_device.  Order, output placement, the size query (d_msgs ==
+ * NULL), the stream, the timing and the allocation rule are
+ * elead_local_batch_device's, with "request" for "record": a group's requests
+ * are adjacent and stepped in array order, each one seeing the state the
+ * previous one left, runs have any length and lie anywhere, the messages are
+ * dense and ordered by request, msg_first counts the messages of the requests
+ * before i also when n_msgs == 0, and no emsg_out at or past *n_msgs is
+ * written.  *n_changed = the ADDED, REMOVED, STOPPED and RELOADED requests
+ * (nullable, as *n_msgs).  A group is its elead_group,
+ * its elead_prop_state, its evote_state, its eready_state and its econf_state.
+ * Per request, lastIndex = nlog - 1 + log_offset:
+ *   kind 1, addNode(node): setProgress(node, 0, lastIndex + 1); pending_conf =
+ *     0.  An id among the first n_peers peer_id keeps its slot and its (match,
+ *     next) are overwritten -- the leader's own id included: Go's quirk is
+ *     kept.  A new id takes slot n_peers, and n_peers grows by one; at n_peers
+ *     == 7 that is EWAL_UNSUPPORTED_ENCODING.  removed[] is NOT cleared for a
+ *     re-added id, as in Go.  ECONF_ADDED.
+ *   kind 2, removeNode(node): delProgress(node); pending_conf = 0;
+ *     removed[node] = true.  The slots after the deleted one move down by one
+ *     with their match and next, the freed slot is zeroed, and the bits of
+ *     evote_state.voted / granted move with their slots.  An id that is not a
+ *     key still enters removed[]; an id already there is not stored twice; a
+ *     15th id is EWAL_UNSUPPORTED_ENCODING.  Go keeps r.votes[node] after the
+ *     delete and the masks cannot: at a CANDIDATE (state 1) whose deleted slot
+ *     has its voted bit set the request is EWAL_UNSUPPORTED_ENCODING; in the
+ *     other two states the votes are not read before the next reset, and the
+ *     bit is dropped.  ECONF_REMOVED.
+ *   kind 3, Step(Message{Type: msgDenied, From: node}), raft.go:376-387 only:
+ *     removed[node]: no state change, and unless node == id one emsg_out {type
+ *     = 8 (msgDenied), to = node, from = id, term = group.term, every other
+ *     field 0}; ECONF_DENIED_BACK.  Otherwise removed[id] = true (a 15th id:
+ *     EWAL_UNSUPPORTED_ENCODING); ECONF_STOPPED.
+ *   kind 4, the removed half of raft.restore, which
+ *     efollow_step_batch_device leaves to the caller: removed[] becomes the
+ *     RemovedNodes range d_u64[removed_off, + n_removed) of d_snaps[group],
+ *     duplicates dropped in first-occurrence order; the slots past the new
+ *     n_removed are zeroed.  More than 14 distinct ids:
+ *     EWAL_UNSUPPORTED_ENCODING.  ECONF_RELOADED.
+ *   any other kind: EWAL_PANIC_CONF_TYPE, panic("unexpected conf type").
+ *   The first request of a group with n_peers > 7 gets
+ *     EWAL_UNSUPPORTED_ENCODING, as everywhere else.
+ * eready_state.soft_dirty is set to 1 when n_peers or one of the first n_peers
+ * peer_id changed (SoftState.Nodes) and when removed[id] changed (ShouldStop,
+ * raft.go:158-162): the next eready_batch_device reports EREADY_SOFT.
+ * A panicking or unsupported request has action ECONF_PANICKED, emits nothing,
+ * leaves every record of its group exactly as it was before that request, and
+ * puts the rest of its group's run at ECONF_NOT_STEPPED; the requests stepped
+ * before it keep their effect.  Results of PANICKED and NOT_STEPPED requests
+ * report the unchanged n_peers and n_removed.
+ * Written, only where a word changed: of a named group n_peers, peer_id[],
+ * match[], next[]; pending_conf; voted, granted; soft_dirty; the econf_state;
+ * d_res; d_msgs below *n_msgs.  Nothing of a group that no request names.
+ * Checked on the device before anything is modified (then every array is
+ * untouched and the counters are 0):
+ *   EWAL_E_INVAL  group >= G; a group's requests not adjacent; a request's pad
+ *                 not 0; a kind-4 request with d_snaps == NULL or its
+ *                 RemovedNodes range outside n_u64, or wrapping; and of a named
+ *                 group: reserved != 0 in any of its five records; n_removed >
+ *                 14; two equal peer_id within the first min(n_peers, 7) slots;
+ *                 pending_conf > 1; soft_dirty > 1; evote_state.state > 2;
+ *                 voted or granted bits at or past n_peers, or granted outside
+ *                 voted
+ *   EWAL_E_NOMEM  the messages exceed msgs_cap (INVAL wins when both occur)
+ * and on the host: EWAL_E_INVAL for a NULL ctx; for d_groups, d_pstate,
+ * d_vstate, d_rstate, d_cstate, d_reqs or d_res NULL while n > 0; for d_u64 ==
+ * NULL with n_u64 > 0; for any record array not 16-byte aligned or d_u64 not
+ * 8-byte aligned; for n or G >= 2^31 - 1.  n == 0: EWAL_OK, counters 0.  A
+ * compute call on the ctx's stream; ewal_last_device_ms covers it; a repeated
+ * call of the same or a smaller shape allocates nothing. */
+int econf_batch_device(ewal_ctx *ctx, elead_group *d_groups, elead_prop_state *d_pstate, evote_state *d_vstate,
+                       eready_state *d_rstate, econf_state *d_cstate, uint64_t G,
+                       const elead_snap *d_snaps /* G, nullable */, const uint64_t *d_u64, uint64_t n_u64,
+                       const econf_req *d_reqs, uint64_t n, econf_result *d_res,
+                       struct emsg_out *d_msgs /* NULL: size query */, uint64_t msgs_cap,
+                       uint64_t *n_msgs, uint64_t *n_changed);
+
+/* econf_scan_committed_device: the ConfChange half of the server loop over
+ * rd.CommittedEntries (etcdserver/server.go:265-286).  d_ready is the
+ * eready_result[n] of an eready_batch_device call; selection i's committed
+ * entries are d_ents[committed_first, + n_committed).  One lane per committed
+ * entry over all selections.  Per entry, in order:
+ *   type 0 (EntryNormal) is the application's and is skipped.
+ *   type 1 (EntryConfChange): ConfChange.Unmarshal over d_data[data_off, +
+ *     data_len).  Empty or nil Data decodes as ConfChange{}: addNode(0), as in
+ *     Go.  Fields 1-3 (ID, Type, NodeID) are varints with a wire-type check,
+ *     OR-ed as the generated code does (a repeated field ORs; Type keeps 32
+ *     bits); field 4 (Context) is bytes, of which only the bounds matter here;
+ *     unknown fields go through proto.Skip with the depth limit and the error
+ *     classes emsg_decode_batch_device has.  It emits one econf_req {group,
+ *     kind = uint32(Type) + 1, node = NodeID, 0} and, at the same position of
+ *     d_applied, what s.w.Trigger(cc.ID, nil) and raftIndex / raftTerm need.
+ *   A type-1 entry whose Unmarshal fails has the status
+ *     emsg_decode_batch_device gives that error (EWAL_ERR_UNEXPECTED_EOF,
+ *     EWAL_ERR_WRONG_TYPE, EWAL_PANIC_BOUNDS, EWAL_NONTERMINATING,
+ *     EWAL_UNSUPPORTED_ENCODING); an entry with data_nil == 2 (its Data is not
+ *     in d_data) has EWAL_UNSUPPORTED_ENCODING; an entry type other than 0 or 1
+ *     has EWAL_ERR_UNEXPECTED_TYPE with detail = the type.  The server panics
+ *     at each (server.go:275-282).  The selection's row names the FIRST such
+ *     entry; it and the later entries of that selection emit nothing, the
+ *     earlier ones keep theirs.
+ * The requests are dense, ordered by selection and then by entry.  Each group
+ * is selected once, so the array goes to econf_batch_device as it lies.
+ * d_reqs == NULL with d_applied == NULL is the size query: d_scan and the
+ * counters are filled.  Nothing but the three outputs is ever written.
+ * *n_reqs = the requests, *n_entries = the committed entries looked at (both
+ * nullable).
+ * Checked on the device before anything is written:
+ *   EWAL_E_INVAL  a selected group >= G; a committed range outside
+ *                 n_ents_total, or wrapping; the committed entries of all
+ *                 selections together >= 2^31 - 1 (ranges that coincide); a
+ *                 scanned type-1 entry's data_nil
+ *                 not 0, 1 or 2, or its Data range outside data_len_total, or
+ *                 wrapping
+ *   EWAL_E_NOMEM  the requests exceed reqs_cap (INVAL wins when both occur)
+ * and on the host: NULL ctx; d_ready or d_scan NULL while n > 0; d_ents NULL
+ * with n_ents_total > 0; d_data NULL with data_len_total > 0; exactly one of
+ * d_reqs and d_applied NULL; d_ready, d_scan, d_reqs, d_applied not 16-byte
+ * aligned, d_ents or d_sel not 8-byte aligned; n, G or n_ents_total >= 2^31 -
+ * 1; d_sel == NULL with n != G: EWAL_E_INVAL.  n == 0: EWAL_OK.  Stream,
+ * timing and allocation as above. */
+typedef struct econf_applied {      /* 32 bytes; a DEVICE array parallel to d_reqs */
+  uint64_t id;                      /* cc.ID */
+  uint64_t index, term;             /* e.Index, e.Term */
+  uint64_t ent_pos;                 /* the entry's position in d_ents */
+} econf_applied;
+typedef struct econf_scan_result {  /* 48 bytes; a DEVICE array of n */
+  int32_t status;                   /* EWAL_OK, or the first failing entry's class */
+  int32_t detail;                   /* EWAL_ERR_UNEXPECTED_TYPE: the entry's type; else 0 */
+  uint64_t req_first, n_reqs;       /* this selection's requests: d_reqs[req_first, + n_reqs) */
+  uint64_t bad_pos;                 /* the failing entry's position in d_ents (0 when status == EWAL_OK) */
+  uint64_t n_scanned;               /* the entries before the failing one; n_committed when none fails */
+  uint64_t pad;                     /* 0 */
+} econf_scan_result;
+int econf_scan_committed_device(ewal_ctx *ctx, const struct eready_result *d_ready,
+                                const uint64_t *d_sel /* as given to eready_batch_device */, uint64_t n, uint64_t G,
+                                const ewal_entry *d_ents, uint64_t n_ents_total,
+                                const void *d_data, uint64_t data_len_total,
+                                econf_scan_result *d_scan,
+                                econf_req *d_reqs /* NULL with d_applied NULL: size query */,
+                                econf_applied *d_applied, uint64_t reqs_cap,
+                                uint64_t *n_reqs, uint64_t *n_entries);
+
+/* econf_gate_batch_device: r.removed[m.From] in front of every step call
+ * (raft.go:376-382), a stable filter over any of the step calls' input arrays.
+ * d_recs is n records of rec_bytes each, rec_bytes in {48, 64, 96}: elead_resp
+ * and elead_local, evote_msg, efollow_msg.  Word 0 of a record is its group;
+ * m.From is its 8-byte word from_word -- 1 for elead_resp, 2 for evote_msg and
+ * efollow_msg -- or, with ECONF_FROM_SELF, the group's id: elead_local, whose
+ * From is the node's own (node.go:222), and etick_batch_device's msgHup.
+ * Per record:
+ *   removed[from], from != id: one emsg_out {type = 8 (msgDenied), to = from,
+ *     from = id, term = group.term, every other field 0}; ECONF_G_DENIED.
+ *   removed[from], from == id: no message; ECONF_G_DROPPED.
+ *   otherwise the record is copied whole to d_pass; ECONF_G_PASS.
+ * d_pass and d_msgs are dense and keep the order of d_recs, so runs stay
+ * adjacent and d_pass goes to its step call as it lies.  d_res[i].pass_pos /
+ * .msg_pos is where record i's copy / message went (0 when it has none).
+ * d_pass == NULL with d_msgs == NULL is the size query.  The groups and the
+ * econf_state are read only; *n_pass and *n_msgs are nullable.
+ * Checked on the device before anything is written:
+ *   EWAL_E_INVAL  a record's group >= G; of a named group n_removed > 14 or
+ *                 econf_state.reserved != 0
+ *   EWAL_E_NOMEM  the copies exceed pass_cap or the messages msgs_cap (INVAL
+ *                 wins when both occur)
+ * and on the host: NULL ctx; d_groups, d_cstate, d_recs or d_res NULL while n
+ * > 0; exactly one of d_pass and d_msgs NULL; rec_bytes not 48, 64 or 96;
+ * from_word neither ECONF_FROM_SELF nor in [1, rec_bytes / 8); an array not
+ * 16-byte aligned; d_pass overlapping d_recs; n or G >= 2^31 - 1:
+ * EWAL_E_INVAL.  n == 0: EWAL_OK.  Stream, timing and allocation as above. */
+#define ECONF_FROM_SELF 0xffffffffu
+enum { ECONF_G_PASS = 1, ECONF_G_DENIED = 2, ECONF_G_DROPPED = 3 };
+typedef struct econf_gate_result {  /* 32 bytes; a DEVICE array of n */
+  int32_t status, action;           /* EWAL_OK; ECONF_G_* */
+  uint64_t pass_pos, msg_pos;
+  uint64_t pad;                     /* 0 */
+} econf_gate_result;
+int econf_gate_batch_device(ewal_ctx *ctx, const elead_group *d_groups, const econf_state *d_cstate, uint64_t G,
+                            const void *d_recs, uint64_t n, uint32_t rec_bytes, uint32_t from_word,
+                            econf_gate_result *d_res,
+                            void *d_pass /* NULL with d_msgs NULL: size query */, uint64_t pass_cap,
+                            struct emsg_out *d_msgs, uint64_t msgs_cap,
+                            uint64_t *n_pass, uint64_t *n_msgs);
+/* For bindings / tests: the sizes of the records above. */
+uint32_t econf_state_size(void);
+uint32_t econf_req_size(void);
+uint32_t econf_result_size(void);
+uint32_t econf_applied_size(void);
+uint32_t econf_scan_result_size(void);
+uint32_t econf_gate_result_size(void);
 
 /* ---- raft ingress: raftpb.Message.Unmarshal, raft/raftpb/raft.pb.go:407-617
  * (called per POST /raft in etcdserver/etcdhttp/http.go:119-146), batched
