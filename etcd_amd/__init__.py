@@ -15,6 +15,7 @@ Product layout:
   raftcompact.py batched log compaction: node.Compact (raft.compact, raftLog.snap, the window's slide)
   rafttick.py  batched Tick: tickElection / tickHeartbeat (elapsed, the msgHup and msgBeat that start the steps)
   raftconf.py  batched membership: ApplyConfChange (addNode / removeNode), the removed[] gate, the ConfChange scan
+  raftnode.py  batched StartNode / RestartNode: a replay's result (or a peer list) into the groups' records
   crc.py       `pkg/crc` digest (chained CRC-32C) over host or device buffers
   raftmsg.py   batched `raftpb.Message` decode (the /raft ingress) and Marshal (the egress)
   shard.py     per-rank shard assignment, the RCCL summary all-reduce and the
@@ -34,6 +35,7 @@ from .raftcompact import compact_batch, compact_batch_device  # noqa: F401
 from .rafttick import tick_batch, tick_batch_device  # noqa: F401
 from .raftconf import (conf_batch, conf_batch_device, scan_committed, scan_committed_device, gate_batch,  # noqa: F401
                        gate_batch_device, pack_cstate, unpack_cstate, removed_u64)
+from .raftnode import node_batch, node_batch_device, reqs_from_batch, entries_device  # noqa: F401
 
 __all__ = ["Context", "OpenAtIndex", "Create", "Encoder", "readall_bytes", "synth_wal", "save_packed", "save_dir",
            "snap_name", "append_batch", "append_batch_device", "lead_step_batch", "lead_step_batch_device",
@@ -41,4 +43,5 @@ __all__ = ["Context", "OpenAtIndex", "Create", "Encoder", "readall_bytes", "synt
            "ready_batch_device", "follow_batch", "follow_batch_device",
            "compact_batch", "compact_batch_device", "tick_batch", "tick_batch_device",
            "conf_batch", "conf_batch_device", "scan_committed", "scan_committed_device", "gate_batch",
-           "gate_batch_device", "pack_cstate", "unpack_cstate", "removed_u64"]
+           "gate_batch_device", "pack_cstate", "unpack_cstate", "removed_u64",
+           "node_batch", "node_batch_device", "reqs_from_batch", "entries_device"]

@@ -61,6 +61,7 @@ PANIC_COMPACT_APPLIED = 45
 PANIC_COMPACT_BOUNDS = 46
 PANIC_CONF_TYPE = 47
 UNSUPPORTED_ENCODING = 48
+PANIC_NONE_ID = 49
 E_HIP, E_INVAL, E_NOMEM, E_NODEVICE, E_TIMEOUT, E_IO = -1, -2, -3, -4, -5, -6
 
 FLAG_SHARD_FALLBACK = 1   # ewal_readall_batch_device verified this shard on its own
@@ -283,6 +284,26 @@ CONF_ADD, CONF_REMOVE, CONF_DENIED, CONF_RELOAD = 1, 2, 3, 4
 CONF_G_PASS, CONF_G_DENIED, CONF_G_DROPPED = 1, 2, 3
 CONF_FROM_SELF = 0xFFFFFFFF
 CONF_MAX_REMOVED = 14
+
+class NodeReq(C.Structure):   # enode_req
+    _fields_ = [("group", C.c_uint64), ("kind", C.c_uint64), ("id", C.c_uint64), ("ents_first", C.c_uint64),
+                ("ents_cap", C.c_uint64), ("src_first", C.c_uint64), ("n_src", C.c_uint64), ("data_delta", C.c_uint64),
+                ("hs_term", C.c_uint64), ("hs_vote", C.c_uint64), ("hs_commit", C.c_uint64), ("snap", C.c_uint64),
+                ("pad", C.c_uint64 * 4)]
+
+
+class NodePeer(C.Structure):   # enode_peer
+    _fields_ = [("id", C.c_uint64), ("ctx_off", C.c_uint64), ("ctx_len", C.c_uint64), ("pad", C.c_uint64)]
+
+
+class NodeResult(C.Structure):   # enode_result
+    _fields_ = [("status", C.c_int32), ("action", C.c_int32), ("nlog", C.c_uint64), ("committed", C.c_uint64),
+                ("log_offset", C.c_uint64), ("n_peers", C.c_uint64), ("data_first", C.c_uint64)]
+
+
+NODE_KIND_NONE, NODE_KIND_RESTART, NODE_KIND_START = 0, 1, 2
+NODE_NONE, NODE_RESTARTED, NODE_RESTARTED_SNAP, NODE_STARTED, NODE_PANICKED = range(5)
+NODE_NO_SNAP = 0xFFFFFFFFFFFFFFFF
 
 SNAP_FIELD_DATA, SNAP_FIELD_UNREC, SNAP_FIELD_NODES, SNAP_FIELD_REMOVED = range(4)
 SEG_UNREC, SEG_ENTRY_UNREC, SEG_ENTRY_DATA, SEG_SNAP_UNREC, SEG_SNAP_DATA, SEG_SNAP_NODE, SEG_SNAP_REMOVED = range(7)
@@ -534,6 +555,15 @@ _SIGS = {
     "econf_applied_size": (C.c_uint32, []),
     "econf_scan_result_size": (C.c_uint32, []),
     "econf_gate_result_size": (C.c_uint32, []),
+    "enode_batch_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp,
+                                     C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64,
+                                     C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64)]),
+    "enode_reqs_from_batch": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]),
+    "ewal_batch_entries_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
+    "enode_req_size": (C.c_uint32, []),
+    "enode_peer_size": (C.c_uint32, []),
+    "enode_result_size": (C.c_uint32, []),
 }
 for _name, (_res, _args) in _SIGS.items():
     if os.environ.get("EWAL_LIB_PATH") and not hasattr(lib, _name):
@@ -565,7 +595,7 @@ def header_symbols(path=HEADER):
     """Every function declared in include/ewal.h."""
     txt = open(path).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead|vote|ready|follow|compact|tick|conf)_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(e(?:wal|snap|commit|msg|log|lead|vote|ready|follow|compact|tick|conf|node)_[a-z0-9_]+)\s*\(", txt)))
 
 
 def status_string(st):
@@ -596,6 +626,6 @@ def check(st, detail=0, record=-1, offset=-1):
         return
     if st == E_NODEVICE:
         raise NoDeviceError(st)
-    if 32 <= st <= 47:
+    if 32 <= st <= 47 or st == PANIC_NONE_ID:
         raise GoPanic(st, detail, record, offset)
     raise EwalError(st, detail, record, offset)

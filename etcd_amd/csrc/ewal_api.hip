@@ -42,6 +42,7 @@
 #include "compact_step.hip"
 #include "tick_step.hip"
 #include "conf_step.hip"
+#include "node_start.hip"
 #include "ewal_stage.h"
 #include "ewal_wire.h"
 
@@ -201,6 +202,7 @@ struct ewal_ctx {
   // econf_scan_committed_device's per-entry records, sized in mid-call)
   DevBuf lstep, lcompact_stage;
   std::vector<uint64_t> bent_first, bnents;   // per shard: first ent in bents, count
+  bool bents_valid = false;                   // the two describe the ctx's LAST ReadAll (a batch that succeeded)
   std::vector<std::vector<ewal_unrec>> bunrec;       // per shard replayed alone: its XXX_unrecognized side list
   std::vector<std::vector<uint8_t>> bunrec_bytes;
   Small *h_small = nullptr;        // host-mapped pinned mirrors (written by k_export_small / k_result)
@@ -1174,6 +1176,7 @@ static int gather_unrec(ewal_ctx *c, const uint8_t *d_buf, const ResultDev &res,
 // (k_check / k_result queued behind k_frame, gated on the device by
 // k_spec_gate); the slow framing paths add their own.
 static int readall_impl(ewal_ctx *c, const uint8_t *d_buf, uint64_t B, uint64_t ri, ewal_result *out) {
+  c->bents_valid = false;   // a single ReadAll (or a batch's shard replayed alone) supersedes the batch's ranges
   bool ev1_final = false;   // c->ev1 already recorded behind the call's last kernel (the fused pass)
   std::memset(out, 0, sizeof(*out));
   out->fail_record = -1;
@@ -2467,7 +2470,10 @@ int ewal_readall_batch_device(ewal_ctx *c, const void *d_buf, uint64_t n_shards,
                               const uint64_t *ri, ewal_result *out) {
   if (!c || (n_shards && (!lens || !ri || !out)) || n_shards >= 0x7fffffffull) return EWAL_E_INVAL;
   EW_CHECK(hipSetDevice(c->device));
-  return readall_batch_impl(c, (const uint8_t *)d_buf, (uint32_t)n_shards, lens, ri, out);
+  c->bents_valid = false;
+  const int rc = readall_batch_impl(c, (const uint8_t *)d_buf, (uint32_t)n_shards, lens, ri, out);
+  c->bents_valid = rc == EWAL_OK;
+  return rc;
 }
 
 int64_t ewal_batch_copy_entries(ewal_ctx *c, uint64_t shard, ewal_entry *out, int64_t cap) {

@@ -328,6 +328,7 @@ const char *ewal_status_string(int st) {
   case EWAL_PANIC_COMPACT_APPLIED: return "panic: raft: compact index exceeds applied index";
   case EWAL_PANIC_COMPACT_BOUNDS: return "panic: compact out of bounds";
   case EWAL_PANIC_CONF_TYPE: return "panic: unexpected conf type";
+  case EWAL_PANIC_NONE_ID: return "panic: cannot use none id";
   case EWAL_UNSUPPORTED_ENCODING: return "unsupported (non-canonical) record encoding";
   case EWAL_E_HIP: return "HIP error";
   case EWAL_E_INVAL: return "invalid argument";

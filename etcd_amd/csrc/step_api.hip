@@ -46,10 +46,10 @@ static int step_begin(ewal_ctx *c, size_t need, size_t head_bytes, size_t claim_
 }
 
 // The one decision point: nothing of the caller's has been modified yet.  The
-// call's n_heads (1 or 2) head records come back in h.
+// call's n_heads (1 to 3) head records come back in h.
 static int step_decide(ewal_ctx *c, const uint8_t *base, uint32_t n_heads, EleadHead *h) {
   EW_CHECK(hipGetLastError());
-  uint8_t hb[2 * STEP_HEAD_SLOT];
+  uint8_t hb[3 * STEP_HEAD_SLOT];
   const size_t bytes = (size_t)(n_heads - 1) * STEP_HEAD_SLOT + sizeof(EleadHead);
   EW_CHECK(hipMemcpyAsync(hb, base, bytes, hipMemcpyDeviceToHost, c->stream));
   EW_CHECK(hipStreamSynchronize(c->stream));
@@ -817,5 +817,135 @@ int econf_gate_batch_device(ewal_ctx *c, const elead_group *d_groups, const econ
   if (int st = step_end(c)) return st;
   if (n_pass) *n_pass = h.n_msgs;
   if (n_msgs) *n_msgs = h.n_committed;
+  return EWAL_OK;
+}
+
+uint32_t enode_req_size(void) { return sizeof(enode_req); }
+uint32_t enode_peer_size(void) { return sizeof(enode_peer); }
+uint32_t enode_result_size(void) { return sizeof(enode_result); }
+
+static_assert(sizeof(enode_req) == 128 && sizeof(enode_peer) == 32 && sizeof(enode_result) == 48 &&
+                  sizeof(EnodeRec) == 48 && offsetof(enode_req, ents_first) == 24 && offsetof(enode_req, n_src) == 48 &&
+                  offsetof(enode_req, hs_term) == 64 && offsetof(enode_req, snap) == 88 &&
+                  offsetof(enode_result, nlog) == 8 && offsetof(enode_result, data_first) == 40 &&
+                  offsetof(econf_state, removed) == 8 && offsetof(eready_state, snapi) == 40,
+              "enode layout");
+int enode_batch_device(ewal_ctx *c, elead_group *d_groups, elead_prop_state *d_pstate, evote_state *d_vstate,
+                       eready_state *d_rstate, econf_state *d_cstate, elead_snap *d_snaps, uint64_t G,
+                       ewal_entry *d_ents, uint64_t n_ents_total, const ewal_entry *d_src, uint64_t n_src_total,
+                       const elead_snap *d_in_snaps, uint64_t n_in_snaps, const uint64_t *d_u64, uint64_t n_u64,
+                       const enode_peer *d_peers, uint64_t n_peers_total, const uint8_t *d_ctx, uint64_t ctx_len,
+                       uint8_t *d_data, uint64_t data_base, uint64_t data_cap, const enode_req *d_reqs, uint64_t n,
+                       enode_result *d_res, uint64_t *n_data, uint64_t *n_copied, uint64_t *n_built) {
+  if (n_data) *n_data = 0;
+  if (n_copied) *n_copied = 0;
+  if (n_built) *n_built = 0;
+  if (!step_args_ok(c, n, G)) return EWAL_E_INVAL;
+  if (n == 0) return EWAL_OK;
+  if (!d_groups || !d_pstate || !d_vstate || !d_rstate || !d_cstate || !d_snaps || !d_reqs || !d_res ||
+      (n_ents_total && !d_ents) || (n_src_total && !d_src) || (n_in_snaps && !d_in_snaps) || (n_u64 && !d_u64) ||
+      (n_peers_total && !d_peers) || (ctx_len && !d_ctx))
+    return EWAL_E_INVAL;
+  if (!aligned(15, {d_groups, d_pstate, d_vstate, d_rstate, d_cstate, d_snaps, d_in_snaps, d_peers, d_reqs, d_res}) ||
+      !aligned(7, {d_ents, d_src, d_u64}))
+    return EWAL_E_INVAL;
+  // scratch: head | bytes head | peers head | claim[G] | rec[n] | cpart | dpart | ppart [2 * workgroups each]
+  const uint32_t blocks = grid_for(n, 256);
+  Carve cv;
+  cv.add(STEP_HEAD_SLOT);
+  const size_t o_dhead = cv.add(STEP_HEAD_SLOT), o_phead = cv.add(STEP_HEAD_SLOT), o_claim = cv.add((size_t)G * 4),
+               o_rec = cv.add((size_t)n * sizeof(EnodeRec)), o_cpart = cv.add((size_t)blocks * 16),
+               o_dpart = cv.add((size_t)blocks * 16), o_ppart = cv.add((size_t)blocks * 16);
+  if (int st = step_begin(c, cv.size(), 3 * STEP_HEAD_SLOT, o_claim, G)) return st;
+  uint8_t *base = c->lstep.as<uint8_t>();
+  EnodeArgs a{};
+  a.groups = d_groups;
+  a.pstate = d_pstate;
+  a.vstate = d_vstate;
+  a.rstate = d_rstate;
+  a.cstate = d_cstate;
+  a.snaps = d_snaps;
+  a.G = G;
+  a.ents = d_ents;
+  a.n_ents_total = n_ents_total;
+  a.src = d_src;
+  a.n_src_total = n_src_total;
+  a.in_snaps = d_in_snaps;
+  a.n_in_snaps = n_in_snaps;
+  a.u64 = d_u64;
+  a.n_u64 = n_u64;
+  a.peers = d_peers;
+  a.n_peers_total = n_peers_total;
+  a.ctx = d_ctx;
+  a.ctx_len = ctx_len;
+  a.data = d_data;
+  a.data_base = data_base;
+  a.in = d_reqs;
+  a.n = n;
+  a.res = d_res;
+  a.head = (EleadHead *)base;
+  a.dhead = (EleadHead *)(base + o_dhead);
+  a.phead = (EleadHead *)(base + o_phead);
+  a.claim = (uint32_t *)(base + o_claim);
+  a.rec = (EnodeRec *)(base + o_rec);
+  a.cpart = (unsigned long long *)(base + o_cpart);
+  a.dpart = (unsigned long long *)(base + o_dpart);
+  a.ppart = (unsigned long long *)(base + o_ppart);
+  a.blocks = blocks;
+  hipLaunchKernelGGL(k_node_count, dim3(blocks), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.cpart, blocks, a.head);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.dpart, blocks, a.dhead);
+  hipLaunchKernelGGL(k_lead_scan, dim3(1), dim3(256), 0, c->stream, a.ppart, blocks, a.phead);
+  EleadHead h[3];                                    // the copied entries and built requests; the bytes; the peers
+  if (int st = step_decide(c, base, 3, h)) return st;
+  if (int st = step_status(h[0], d_data, h[1].n_msgs, data_cap)) return st;
+  // the lanes of the copy and marshal passes are 32-bit workgroup ordinals
+  if (h[0].n_msgs >= 0x7fffffffull * 256 || h[2].n_msgs >= 0x7fffffffull * 256) return EWAL_E_INVAL;
+  if (d_data) {
+    hipLaunchKernelGGL(k_node_apply<true>, dim3(blocks), dim3(256), 0, c->stream, a);
+    if (h[0].n_msgs) {
+      a.n_work = h[0].n_msgs;
+      hipLaunchKernelGGL(k_node_copy, dim3(grid_for(a.n_work, 256)), dim3(256), 0, c->stream, a);
+    }
+    if (h[2].n_msgs) {
+      a.n_work = h[2].n_msgs;
+      hipLaunchKernelGGL(k_node_marshal, dim3(grid_for(a.n_work, 256)), dim3(256), 0, c->stream, a);
+    }
+  } else {
+    hipLaunchKernelGGL(k_node_apply<false>, dim3(blocks), dim3(256), 0, c->stream, a);
+  }
+  if (int st = step_end(c)) return st;
+  if (n_data) *n_data = h[1].n_msgs;
+  if (n_copied) *n_copied = h[0].n_msgs;
+  if (n_built) *n_built = h[0].n_committed;
+  return EWAL_OK;
+}
+
+int ewal_batch_entries_device(ewal_ctx *c, const ewal_entry **d_ents, uint64_t *n_total) {
+  if (!c || !d_ents || !n_total || !c->bents_valid) return EWAL_E_INVAL;
+  uint64_t end = 0;
+  for (size_t s = 0; s < c->bnents.size(); ++s) end = std::max(end, c->bent_first[s] + c->bnents[s]);
+  *d_ents = end ? c->bents.as<ewal_entry>() : nullptr;
+  *n_total = end;
+  return EWAL_OK;
+}
+
+int enode_reqs_from_batch(ewal_ctx *c, const ewal_result *res, uint64_t n_shards, const uint64_t *shard_off,
+                          enode_req *h_reqs) {
+  if (!c || !c->bents_valid || n_shards != c->bnents.size() || (n_shards && (!res || !shard_off || !h_reqs)))
+    return EWAL_E_INVAL;
+  for (uint64_t s = 0; s < n_shards; ++s) {
+    enode_req &r = h_reqs[s];
+    const bool ok = res[s].status == EWAL_OK && res[s].n_unrec == 0;
+    r.group = s;
+    r.kind = ok ? 1 : 0;
+    r.src_first = c->bent_first[s];
+    r.n_src = c->bnents[s];
+    r.data_delta = shard_off[s];
+    r.hs_term = res[s].has_state ? res[s].state_term : 0;
+    r.hs_vote = res[s].has_state ? res[s].state_vote : 0;
+    r.hs_commit = res[s].has_state ? res[s].state_commit : 0;
+    r.pad[0] = r.pad[1] = r.pad[2] = r.pad[3] = 0;
+  }
   return EWAL_OK;
 }

@@ -1,6 +1,6 @@
 // step_common.hip -- what the batched raft step files share (log_append.hip,
 // lead_step.hip, lead_prop.hip, vote_step.hip, ready_step.hip, follow_step.hip,
-// compact_step.hip, tick_step.hip, conf_step.hip): the call's head record and error classes, the claim word,
+// compact_step.hip, tick_step.hip, conf_step.hip, node_start.hip): the call's head record and error classes, the claim word,
 // the workgroup sums and scan, k_lead_scan, the record loaders and the
 // write-back of a group's changed words.  DESIGN.md, "The step calls' common
 // skeleton", has how a step call is put together from them.

@@ -63,6 +63,7 @@ enum {
                                       fail_offset name it, in a batch for that shard
                                       alone), esnap_verify_packed gives it as the file's
                                       status, emsg_decode_batch_device as the message's */
+  EWAL_PANIC_NONE_ID = 49,         /* panic("cannot use none id"), raft/raft.go:136-138 */
   /* infrastructure (negative) */
   EWAL_E_HIP = -1,
   EWAL_E_INVAL = -2,
@@ -230,6 +231,15 @@ int ewal_readall_batch_device(ewal_ctx *ctx, const void *d_buf, uint64_t n_shard
 /* After ewal_readall_batch_device: shard s's ents (Data offsets relative to
  * the shard).  Returns the number copied (<= cap) or a negative error. */
 int64_t ewal_batch_copy_entries(ewal_ctx *ctx, uint64_t shard, ewal_entry *out, int64_t cap);
+/* After ewal_readall_batch_device: the ctx-owned DEVICE array that
+ * ewal_batch_copy_entries reads, and its length in entries (NULL and 0 when
+ * the batch returned no entry).  Shard s's ents are the range
+ * enode_reqs_from_batch (below) names.  The array is valid until the next
+ * pipeline call on the ctx (any ReadAll, batch or single); the step calls,
+ * enode_batch_device included, leave it alone.  Read only.  EWAL_E_INVAL when
+ * the ctx's last ReadAll was not a batch that returned EWAL_OK (a single
+ * ReadAll in between supersedes the batch's ranges). */
+int ewal_batch_entries_device(ewal_ctx *ctx, const ewal_entry **d_ents, uint64_t *n_total);
 /* After ewal_readall_batch_device: shard s's XXX_unrecognized side list
  * (ewal_unrec, ent = index into that shard's ents or -1 for its HardState)
  * and the bytes it indexes.  Return the number copied (<= cap). */
@@ -1930,6 +1940,158 @@ uint32_t econf_result_size(void);
 uint32_t econf_applied_size(void);
 uint32_t econf_scan_result_size(void);
 uint32_t econf_gate_result_size(void);
+
+/* ---- StartNode / RestartNode: raft.StartNode and raft.RestartNode
+ * (raft/node.go:125-161) with newRaft(id, nil, ...) (raft/raft.go:135-154),
+ * newLog (raft/log.go:26-34), raft.restore (raft.go:535-554, log.go:185-192),
+ * loadState / loadEnts (raft.go:597-606, log.go:40-43), StartNode's
+ * ConfChange.Marshal entries (raft/raftpb/raft.pb.go:1108-1130) and the locals
+ * node.run starts with (node.go:194-197).  Batched over n requests, at most one
+ * per group, for G raft groups: the call that BUILDS the records every call
+ * above runs on -- a group's elead_group, elead_prop_state, evote_state,
+ * eready_state and econf_state, d_snaps[g] and the window of d_ents -- from a
+ * batch replay's result (kind 1) or from a list of peers (kind 2).  With
+ * ewal_batch_entries_device and enode_reqs_from_batch a replay's entries reach
+ * their groups' windows without leaving the device.  All arithmetic is Go's
+ * uint64 and wraps; lastIndex = nlog - 1 + log_offset. */
+typedef struct enode_req {          /* 128 bytes; one node to build; a DEVICE array of n */
+  uint64_t group;                   /* which row of the five record arrays (and d_snaps) it builds */
+  uint64_t kind;                    /* 0 none (e.g. a shard whose ReadAll failed), 1 RestartNode, 2 StartNode */
+  uint64_t id;                      /* raft id */
+  uint64_t ents_first, ents_cap;    /* the window given to the group in d_ents */
+  uint64_t src_first, n_src;        /* kind 1: ents = d_src[src_first, + n_src) (ReadAll's ents);
+                                       kind 2: peers = d_peers[src_first, + n_src) */
+  uint64_t data_delta;              /* kind 1: added to data_off where data_nil == 0 (the shard's base in the WAL buffer) */
+  uint64_t hs_term, hs_vote, hs_commit;  /* kind 1: st (zeros when ReadAll had no state record) */
+  uint64_t snap;                    /* kind 1: row of d_in_snaps, or UINT64_MAX: snapshot == nil */
+  uint64_t pad[4];                  /* 0 */
+} enode_req;
+/* raft.Peer; Context = d_ctx[ctx_off, + ctx_len) */
+typedef struct enode_peer { uint64_t id, ctx_off, ctx_len, pad; } enode_peer;   /* 32 bytes */
+enum { ENODE_NONE = 0,              /* kind 0: nothing built */
+       ENODE_RESTARTED = 1,         /* kind 1, no snapshot or restore returned false */
+       ENODE_RESTARTED_SNAP = 2,    /* kind 1, restore returned true */
+       ENODE_STARTED = 3,           /* kind 2 */
+       ENODE_PANICKED = 4 };        /* Go panics (status says where), or the request is unsupported */
+typedef struct enode_result {       /* 48 bytes; a DEVICE array of n */
+  int32_t status, action;           /* EWAL_OK, EWAL_PANIC_NONE_ID, EWAL_UNSUPPORTED_ENCODING; ENODE_* */
+  uint64_t nlog, committed, log_offset, n_peers;  /* as built; 0 for NONE and PANICKED */
+  uint64_t data_first;              /* kind 2: its ConfChange bytes start at d_data[data_first]; else 0 */
+} enode_result;
+/* Per request, in Go's order:
+ *   both kinds: id == 0 is EWAL_PANIC_NONE_ID.  newRaft, then
+ *     becomeFollower(0, None): term, vote, lead, state and elapsed 0; votes
+ *     (voted, granted), prs (n_peers and the three peer arrays) and removed
+ *     empty; pending_conf 0; the log is the dummy entry alone with log_offset,
+ *     committed, applied and unstable 0 and the snapshot empty.
+ *   kind 1, RestartNode(id, _, _, snapshot, st, ents):
+ *     snap != UINT64_MAX: restore(s), s = d_in_snaps[snap].  s.index <= 0
+ *       returns false and nothing of s is taken, not even its Nodes (Go's
+ *       quirk, kept).  Otherwise log_offset = committed = applied = s.index,
+ *       d_snaps[g] = s, prs is rebuilt from s.Nodes = d_u64[nodes_off, +
+ *       n_nodes) by the slot rule efollow_step_batch_device documents (the
+ *       distinct ids take the slots in first-occurrence order; the slot whose
+ *       id equals id gets (match, next) = (s.index, s.index + 1), the others
+ *       (0, s.index + 1)), and removed[] from s.RemovedNodes = d_u64[
+ *       removed_off, + n_removed) by econf_batch_device's kind-4 rule
+ *       (duplicates dropped in first-occurrence order).  ENODE_RESTARTED_SNAP.
+ *     loadState: term = hs_term, vote = hs_vote, committed = hs_commit,
+ *       unconditionally: there is no clamp, and a zero HardState sets committed
+ *       back to 0 after a restore, as Go does.
+ *     loadEnts: the log IS the n_src entries (the entry a restore left is
+ *       replaced with the rest): d_ents[ents_first + j] = d_src[src_first + j],
+ *       data_off rebased by data_delta where data_nil == 0 (an entry with
+ *       data_nil == 2 is copied untouched, and so is one with data_nil == 1,
+ *       whose data_off a replay leaves undefined); nlog = n_src; unstable = log_offset
+ *       + n_src.  With n_src == 0 nlog is 0 and lastIndex wraps, as everywhere
+ *       else.  The entries' own index fields are not examined.
+ *     node.run's locals, the eready_state: hs_* = st, lead 0, state 0, snapi =
+ *       d_snaps[g].index, applied = s.index or 0, soft_dirty 0.
+ *   kind 2, StartNode(id, peers, _, _): slot 0 of the window is the dummy
+ *     entry {0, 0, 0, 0, type 0, data_nil 1}; slot 1 + i is {term 1, index i +
+ *     1, type 1 (EntryConfChange), data_nil 0} whose Data is ConfChange{ID 0,
+ *     Type 0 (AddNode), NodeID peers[i].id, Context}.Marshal(): 08 00 10 00 18
+ *     v(id) 22 v(len) ctx, every field written.  The bytes of all requests are
+ *     dense in d_data in request order, then peer order: request i's start at
+ *     d_data[data_first], and an entry's data_off = data_base + its position
+ *     in d_data (data_base: where d_data lies in the buffer the entries' Data
+ *     offsets mean).  nlog = 1 + n_src, committed = n_src, unstable = 0,
+ *     n_peers = 0: the peers arrive when the committed entries are applied
+ *     (econf_scan_committed_device, econf_batch_device).  eready_state.hs_* =
+ *     {0, 0, n_src}: StartNode sets raftLog.committed without a Step
+ *     (node.go:141-142), so Go's first Ready carries no HardState; this is the
+ *     seeding eready_batch_device's comment leaves to the caller, done here.
+ *     Everything else is 0.  ENODE_STARTED.
+ *   kind 0: ENODE_NONE, nothing is read or written but d_res.
+ * EWAL_UNSUPPORTED_ENCODING, reported, never guessed, for a restore that runs
+ * (s.index > 0) with n_nodes > 64, more than 7 distinct Nodes or more than 14
+ * distinct RemovedNodes.
+ * Written: EVERY word of the five records of a built group, reserved words as
+ * 0 -- the "changed words only" rule of the step calls does not apply, the
+ * records' previous content is undefined and not read; d_snaps[g] (all zero
+ * without a restore); the window's first nlog slots; d_data below *n_data;
+ * d_res.  Slots past nlog, groups no request names and the groups of kind-0
+ * requests are untouched.  A panicking or unsupported request has action
+ * ENODE_PANICKED, every result field but status and action 0, and leaves its
+ * group and its window exactly as they were.
+ * d_data == NULL is the size query: d_res, *n_data (the ConfChange bytes),
+ * *n_copied (the entries copied) and *n_built (the RESTARTED, RESTARTED_SNAP
+ * and STARTED requests) are filled and nothing else is modified (all three
+ * counters nullable).  A call without a kind-2 request still needs a non-NULL
+ * d_data to build; data_cap may be 0 then.
+ * The source ranges must not overlap the named groups' windows, and the
+ * windows must not overlap each other; d_in_snaps must not be d_snaps, nor
+ * share a row with it: the caller's contract, as in efollow_step_batch_device.
+ * Checked on the device before anything is modified (then every array is
+ * untouched and the counters are 0):
+ *   EWAL_E_INVAL  group >= G; a group named by two requests (kind 0 included);
+ *                 kind > 2; pad != 0; and for kinds 1 and 2: a window outside
+ *                 n_ents_total, or wrapping; a source range outside n_src_total
+ *                 (kind 1) or n_peers_total (kind 2), or wrapping; snap neither
+ *                 UINT64_MAX nor < n_in_snaps; a Nodes or RemovedNodes range of
+ *                 that snapshot outside n_u64 (whatever s.index is); a peer's
+ *                 Context range outside ctx_len; enode_peer.pad != 0
+ *   EWAL_E_NOMEM  n_src > ents_cap (kind 1); 1 + n_src > ents_cap (kind 2); the
+ *                 ConfChange bytes exceed data_cap (INVAL wins when both occur)
+ * and at the decision point, with the same guarantee: EWAL_E_INVAL when the
+ * entries to copy, or the peers to marshal, number 2^31 x 256 or more over the
+ * whole call (the copy and marshal passes' lanes are 32-bit workgroup
+ * ordinals).  The three totals (entries, peers, bytes) are uint64 sums over
+ * the requests; requests may name overlapping source or peer ranges, so the
+ * array lengths do not bound them, and a sum that wraps is not detected: keep
+ * the call's totals below 2^64.
+ * and on the host: EWAL_E_INVAL for a NULL ctx; for any of the six group
+ * arrays, d_reqs or d_res NULL while n > 0; for d_ents, d_src, d_in_snaps,
+ * d_u64, d_peers or d_ctx NULL with a length > 0; for a record array (d_peers
+ * and d_in_snaps included) not 16-byte aligned or d_ents, d_src, d_u64 not
+ * 8-byte aligned; for n or G >= 2^31 - 1.  n == 0: EWAL_OK, counters 0.  A
+ * compute call on the ctx's stream; ewal_last_device_ms covers it; a repeated
+ * call of the same or a smaller shape allocates nothing. */
+int enode_batch_device(ewal_ctx *ctx, elead_group *d_groups, elead_prop_state *d_pstate, evote_state *d_vstate,
+                       eready_state *d_rstate, econf_state *d_cstate, elead_snap *d_snaps, uint64_t G,
+                       ewal_entry *d_ents, uint64_t n_ents_total,
+                       const ewal_entry *d_src, uint64_t n_src_total,
+                       const elead_snap *d_in_snaps, uint64_t n_in_snaps, const uint64_t *d_u64, uint64_t n_u64,
+                       const enode_peer *d_peers, uint64_t n_peers_total, const uint8_t *d_ctx, uint64_t ctx_len,
+                       uint8_t *d_data /* NULL: size query */, uint64_t data_base, uint64_t data_cap,
+                       const enode_req *d_reqs, uint64_t n, enode_result *d_res,
+                       uint64_t *n_data, uint64_t *n_copied, uint64_t *n_built);
+/* Host only: the requests of a batch replay.  res[n_shards] is what
+ * ewal_readall_batch_device just returned on ctx, shard_off[s] the place of
+ * shard s in the buffer the entries' Data offsets shall mean.  Request s gets
+ * group = s; kind = 1 when res[s].status == EWAL_OK and res[s].n_unrec == 0,
+ * else 0; src_first and n_src = shard s's range of the array
+ * ewal_batch_entries_device returns; data_delta = shard_off[s]; hs_* =
+ * res[s]'s HardState (zeros without a state record); pad = 0.  id, ents_first,
+ * ents_cap and snap are not touched: the caller fills them, before or after.
+ * EWAL_E_INVAL: a NULL argument, n_shards is not the last batch's, or the
+ * ctx's last ReadAll was not a batch that returned EWAL_OK. */
+int enode_reqs_from_batch(ewal_ctx *ctx, const ewal_result *res, uint64_t n_shards, const uint64_t *shard_off,
+                          enode_req *h_reqs);
+/* For bindings / tests: the sizes of the three records. */
+uint32_t enode_req_size(void);
+uint32_t enode_peer_size(void);
+uint32_t enode_result_size(void);
 
 /* ---- raft ingress: raftpb.Message.Unmarshal, raft/raftpb/raft.pb.go:407-617
  * (called per POST /raft in etcdserver/etcdhttp/http.go:119-146), batched
